@@ -17,6 +17,14 @@ processes (before touching the GPU) when WORLD_SIZE is not set; the driver's for
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 runs directly. Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the result line.
+`--full` adds every other leg: HIP events around the bf16 NT GEMM launches of the timed steps (the
+`roofline` entry), the eval forward in bf16 and MX-fp8 (`forward`), config 2, the RN50 backbone,
+config 5 and the CPU oracle baseline; --no-gemm-timer, --fwd-steps 0, --no-config2, --no-rn50,
+--no-config5 and --no-cpu-baseline drop single legs of it.
+`--dump-outputs DIR` writes what the last timed step handed its caller (dump_outputs) as .npy
+files: the inputs are seeded, so two builds of the library can be compared array for array.
 """
 import argparse
 import json
@@ -131,6 +139,33 @@ class GemmTimer:
         n = len(self.recs)
         return {"launches": n, "avg_us": t / n * 1e6, "avg_gflop": f / n / 1e9,
                 "achieved_tflops": f / t / 1e12, "avg_alg_bytes": b / n}
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept of every flat buffer (2 stores x 3 buffers x 4 MB = 24 MB)
+
+
+def dump_outputs(directory, loss, opt):
+    """What train_step hands its caller after the last timed step, as float32 <name>.npy: the mean
+    loss it returns and, from the buffers it updates in place, DUMP_SAMPLE elements of every flat
+    store's fp32 master weights and AdamW moments at fixed seeded positions (the gradients are
+    zero again when the step returns; the moments carry them)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+
+    def save(name, t):
+        np.save(os.path.join(directory, name + ".npy"), t.detach().float().cpu().numpy())
+
+    save("loss", loss.reshape(1))
+    for i, s in enumerate(opt.stores):
+        n = s.master.numel()
+        if n > DUMP_SAMPLE:
+            g = torch.Generator(device="cpu").manual_seed(424243 + i)
+            idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).to(s.master.device)
+        else:
+            idx = torch.arange(n, device=s.master.device)
+        save(f"store{i}_master", s.master[idx])
+        save(f"store{i}_exp_avg", opt.m[i][idx])
+        save(f"store{i}_exp_avg_sq", opt.v[i][idx])
 
 
 def _newest_profile(pattern):
@@ -454,6 +489,13 @@ def main():
     ap.add_argument("--micro", type=int, default=32,
                     help="stories per micro-batch (default: the whole per-GPU batch in one pass; "
                          "16 measured 1.8%% slower on the same box, profiles/r2_v14_micro_ab.txt)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs (GEMM roofline events, eval forward, config 2, "
+                         "RN50, config 5, CPU baseline); the --no-* flags and --fwd-steps 0 drop "
+                         "single legs of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (loss, sampled "
+                         "weights and AdamW moments) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gemm-timer", action="store_true")
     ap.add_argument("--fwd-micro", type=int, default=0,
@@ -509,7 +551,7 @@ def main():
         mbs.append({k: v[o:o + args.micro] for k, v in data.items()})
 
     timer = GemmTimer()
-    if not args.no_gemm_timer:
+    if args.full and not args.no_gemm_timer:
         timer.install()
     for _ in range(args.warmup):
         train_step(model, opt, mbs, reducer)
@@ -547,11 +589,13 @@ def main():
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, opt)
 
     # North-star forward check (stories/s_fwd x fwd FLOP/story / peak): the same
     # batch, eval mode (no dropout), no autograd graph, timed like the training steps.
     fwd_dt = None
-    if args.fwd_steps > 0:
+    if args.full and args.fwd_steps > 0:
         model.eval()
         # inference keeps no activations for a backward: the whole per-GPU batch in one pass
         # (--fwd-micro stories per call), bigger GEMMs and half the launches of the training split
@@ -694,22 +738,23 @@ def main():
                 "frac_profile_note": "the same average GFLOP per launch over the average duration of "
                                      "the bf16 gemm256_nt_kernel launches in the cited rocprofv3 kernel "
                                      "statistics (a separate, profiled run of this workload)"})
-    if world == 1 and not args.no_config2:
+    legs = args.full and world == 1  # the secondary legs: one GPU, --full only
+    if legs and not args.no_config2:
         try:
             out["config2"] = bench_config2(32, max(30, args.steps), max(3, args.warmup), dev)
         except Exception as e:  # a secondary leg: reported, never required for the headline
             out["config2"] = {"error": repr(e)}
-    if world == 1 and not args.no_rn50:
+    if legs and not args.no_rn50:
         try:
             out["config3_rn50"] = bench_config3_rn50(32, 16, max(2, args.steps), 1, dev)
         except Exception as e:  # a secondary leg: reported, never required for the headline
             out["config3_rn50"] = {"error": repr(e)}
-    if world == 1 and not args.no_config5:
+    if legs and not args.no_config5:
         try:
             out["config5"] = bench_config5(4, 2, 2, 1, dev)
         except Exception as e:
             out["config5"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if legs and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(args.config)
             out["cpu_baseline"]["tflops"] = out["cpu_baseline"]["value"] * 3 * fwd / 1e12

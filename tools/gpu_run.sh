@@ -7,7 +7,7 @@
 # Steps:
 #   tests[:ARGS]     pytest -m gpu over ARGS (default: tests)      -> pytest_gpu.log
 #   smoke            __graft_entry__.smoke()                          -> smoke.log
-#   bench[:ARGS]     python bench.py ARGS                             -> bench.log (appended)
+#   bench[:ARGS]     python bench.py ARGS (--full: every leg)         -> bench.log (appended)
 #   py:SCRIPT ARGS   python SCRIPT ARGS                               -> <script>.log (appended)
 #   bin:PROG ARGS    a program built here beforehand (e.g. tools/bw_mix) -> <prog>.log (appended)
 #   attn-ab:NAME     rocprof kernel stats of tools/attn_bench.py, ab/libmmseq_NAME.so vs the
