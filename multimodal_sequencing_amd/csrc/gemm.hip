@@ -613,11 +613,11 @@ __global__ __launch_bounds__(256, 2) void gemm_ring_kernel(GemmArgs a, int tiles
 // out[m] += sum_s slab[s][m] (fused bias-gradient partials of the split-K wgrad; fixed order).
 // S = splits x column tiles runs to ~100 partials: a block takes 32 columns and spreads the
 // partials over 8 slices (slice j sums s = j, j + 8, ...), then adds the 8 slice sums in order
-__global__ __launch_bounds__(256) void cs_reduce_kernel(int M, int S, const float* __restrict__ slab,
-                                                        float* __restrict__ out) {
+__device__ __forceinline__ void cs_reduce_block(int blk, int M, int S, const float* __restrict__ slab,
+                                                float* __restrict__ out) {
   __shared__ float red[8][32];
   const int c = threadIdx.x & 31, j = threadIdx.x >> 5;
-  const int m = blockIdx.x * 32 + c;
+  const int m = blk * 32 + c;
   float v = 0.f;
   if (m < M) {
 #pragma unroll 4
@@ -666,11 +666,11 @@ __global__ __launch_bounds__(256) void splitk_epi_kernel(GemmArgs a, int S, cons
   }
 }
 
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(int M, int N, int S, const float* __restrict__ slab,
-                                                            float* __restrict__ C, int64_t ldc,
-                                                            int accumulate) {
+__device__ __forceinline__ void splitk_reduce_block(int blk, int nblk, int M, int N, int S,
+                                                    const float* __restrict__ slab,
+                                                    float* __restrict__ C, int64_t ldc, int accumulate) {
   const int64_t total4 = (int64_t)M * N / 4;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+  for (int64_t i = (int64_t)blk * 256 + threadIdx.x; i < total4; i += (int64_t)nblk * 256) {
     const int64_t e = i * 4;
     const int m = e / N, n = e % N;
     f32x4 v = *reinterpret_cast<const f32x4*>(slab + e);
@@ -679,6 +679,24 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(int M, int N, int S,
     if (accumulate) v += *reinterpret_cast<const f32x4*>(cp);
     *reinterpret_cast<f32x4*>(cp) = v;
   }
+}
+
+__global__ __launch_bounds__(256) void splitk_reduce_kernel(int M, int N, int S, const float* __restrict__ slab,
+                                                            float* __restrict__ C, int64_t ldc,
+                                                            int accumulate) {
+  splitk_reduce_block(blockIdx.x, gridDim.x, M, N, S, slab, C, ldc, accumulate);
+}
+
+// Both reductions of a weight gradient with the fused bias gradient in one launch: the first
+// `wblocks` blocks reduce the split-K slab into C (none when the K range was not split), the
+// (M + 31) / 32 blocks after them the bias partial rows into `cs_out`; each sum as above.
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(int M, int N, int S, const float* __restrict__ slab,
+                                                           float* __restrict__ C, int64_t ldc,
+                                                           int wblocks, int cs_S,
+                                                           const float* __restrict__ cs_slab,
+                                                           float* __restrict__ cs_out) {
+  if ((int)blockIdx.x < wblocks) splitk_reduce_block(blockIdx.x, wblocks, M, N, S, slab, C, ldc, 1);
+  else cs_reduce_block(blockIdx.x - wblocks, M, cs_S, cs_slab, cs_out);
 }
 
 template <typename TO>
@@ -882,8 +900,9 @@ extern "C" int64_t mmseq_gemm_workspace_size(int M, int N, int K) {
 
 // Weight gradient with the fused bias gradient (include/mmseq.h): C[M][N] += A^T B and
 // bias_grad[m] += sum_k A[k][m]. bf16 operands with an eligible shape take the 256 x 256 TN
-// kernel (column sums of the A fragments on the VALU beside the MFMAs); anything else runs
-// mmseq_gemm plus a separate column-sum kernel.
+// kernel (column sums of the A fragments on the VALU inside the MFMA bursts, then one launch that
+// reduces the split-K slab and the bias partial rows); anything else runs mmseq_gemm plus a
+// separate column-sum kernel.
 extern "C" mmseq_status mmseq_gemm_wgrad(int M, int N, int K, const void* A, int64_t lda,
                                          const void* B, int64_t ldb, float* C, int64_t ldc,
                                          float* bias_grad, mmseq_dtype in_dtype, int variant,
@@ -926,23 +945,25 @@ extern "C" mmseq_status mmseq_gemm_wgrad(int M, int N, int K, const void* A, int
     t.slab = g_slab;
     t.cs = bias_grad;
     // the bias gradient's partials [split][column tile][M] (balanced over the column tiles, summed
-    // in fixed order by cs_reduce); without workspace room the first column tile adds them directly
+    // in fixed order by wgrad_reduce_kernel); without workspace room the first column tile adds
+    // them directly
     const int64_t slab_c = t.splitk > 1 ? (int64_t)t.splitk * M * N : 0;
     t.cs_slab = bias_grad && g_slab &&
                         (slab_c + (int64_t)t.splitk * tn256 * M) * 4 <= g_slab_bytes
                     ? g_slab + slab_c : nullptr;
     hipError_t e2 = hipSuccess;
     if (mmseq_gemm256_tn(t, s, &e2)) {
-      if (e2 == hipSuccess && t.splitk > 1) {
-        const int64_t t4 = (int64_t)M * N / 4;
-        const unsigned blocks = (unsigned)((t4 + 255) / 256 < 4096 ? (t4 + 255) / 256 : 4096);
+      const int64_t t4 = (int64_t)M * N / 4;
+      const unsigned blocks =
+          t.splitk > 1 ? (unsigned)((t4 + 255) / 256 < 4096 ? (t4 + 255) / 256 : 4096) : 0;
+      if (e2 == hipSuccess && t.cs_slab) {  // the slab and the bias partial rows in one launch
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks + (M + 31) / 32), dim3(256), 0, s, M, N,
+                           t.splitk, g_slab, C, ldc, (int)blocks, t.splitk * tn256, t.cs_slab,
+                           bias_grad);
+        e2 = hipGetLastError();
+      } else if (e2 == hipSuccess && blocks) {
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, M, N, t.splitk,
                            g_slab, C, ldc, 1);
-        e2 = hipGetLastError();
-      }
-      if (e2 == hipSuccess && t.cs_slab) {
-        hipLaunchKernelGGL(cs_reduce_kernel, dim3((M + 31) / 32), dim3(256), 0, s, M,
-                           t.splitk * tn256, t.cs_slab, bias_grad);
         e2 = hipGetLastError();
       }
       if (e2 != hipSuccess) return mmseq_set_error(MMSEQ_EHIP, "gemm_wgrad: %s", hipGetErrorString(e2));

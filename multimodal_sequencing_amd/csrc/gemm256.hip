@@ -711,7 +711,18 @@ _Pragma("unroll") \
 // k order inside a 32-step is permuted identically for both operands (lane group g supplies
 // k {4g..4g+3} U {16+4g..16+4g+3}). Rows past the split's end are zero-filled by the buffer range.
 // Output: fp32, raw partial slab [split][M][N] when split > 1, else C (+)= the tile.
+// Two instances. CS = false (no bias gradient): the MFMA bursts alone. CS = true: the column sums
+// of dY for the bias gradient ride inside the bursts. A wave's register slots hold its A tiles
+// rotated by wc, so the tile it sums is the first slot of every phase; the 16 VALU of a phase's
+// sum (unpack, pair adds, chain) are pinned two behind each of the first eight MFMAs with
+// sched_group_barrier, where the MFMA pipe is busy anyway; a block-uniform mask instead of a
+// branch turns the sum off in K-tiles that belong to another column tile, so a phase stays one
+// basic block. (In front of the burst the sums cost 9-12 % of the kernel; a branch around two
+// copies of the burst spilled 230 VGPRs; without the split in two instances the bias-free calls
+// carried the accumulator copies the allocator made for the branch.) 217 VGPRs with the sums, 228
+// without, every accumulator in place, no scratch in either.
 // ---------------------------------------------------------------------------------------------
+template <bool CS>
 __global__ __launch_bounds__(512, 1) void gemm256_tn_kernel(GemmArgs a, int tiles_n, int ntiles) {
   __shared__ __attribute__((aligned(16))) unsigned short smem[2 * 2 * G_LDA_HALF];  // 128 KB
   const int tid = threadIdx.x, lane = tid & 63;
@@ -762,12 +773,17 @@ __global__ __launch_bounds__(512, 1) void gemm256_tn_kernel(GemmArgs a, int tile
 
   // transposed fragment reads: lane (g, ii = 4 q' + p) reads k-row 4g + q' (+16) at column
   // base + 4p, i.e. chunk 2 (tile) + (p >> 1) XOR-swizzled by ((4g + q') & 7) << 1
-  const int g = lane >> 4, ii = lane & 15, qq = ii >> 2, pp = ii & 3;
-  const int kr = 4 * g + qq, t8 = kr & 7;
+  const int qq = (lane & 15) >> 2, pp = lane & 3;
+  const int kr = 4 * (lane >> 4) + qq, t8 = kr & 7;
   int fA[8], fB[4];
+  // Register slot i of a wave holds A tile ti(i): the four tiles of a phase rotated by wc, so the
+  // tile whose column sums the wave owns (wc, 4 + wc) is always the phase's first slot and the
+  // bias sums need no branch on wc inside the MFMA burst. Every accumulator still sees its K-tiles
+  // in the same order, so the rotation changes no result.
+  auto ti = [&](int i) { return (i & 4) | ((i + wc) & 3); };
 #pragma unroll
   for (int i = 0; i < 8; ++i)
-    fA[i] = kr * 256 + (((wr * 16 + 2 * i + (pp >> 1)) ^ (t8 << 1)) << 3) + (pp & 1) * 4;
+    fA[i] = kr * 256 + (((wr * 16 + 2 * ti(i) + (pp >> 1)) ^ (t8 << 1)) << 3) + (pp & 1) * 4;
 #pragma unroll
   for (int j = 0; j < 4; ++j)
     fB[j] = G_LDA_HALF + kr * 256 + (((wc * 8 + 2 * j + (pp >> 1)) ^ (t8 << 1)) << 3) + (pp & 1) * 4;
@@ -785,24 +801,28 @@ __global__ __launch_bounds__(512, 1) void gemm256_tn_kernel(GemmArgs a, int tile
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   bf16x8_t fa[8], fb[4];
-  // fused bias gradient (column sums of A = dY): wave wc sums A tiles i = wc (cs0) and 4 + wc
-  // (cs1) on the VALU beside its MFMAs; lane (g, ii) holds the partial over its k-slots of column
-  // wr*128 + i*16 + ii. With a partial slab (a.cs_slab) the tiles_n blocks that share an M-tile
+  // fused bias gradient (column sums of A = dY): wave wc sums A tiles wc (cs0) and 4 + wc (cs1),
+  // its register slots 0 and 4, on the VALU between its MFMAs; lane (g, ii) holds the partial
+  // over its k-slots of column wr*128 + i*16 + ii. With a partial slab (a.cs_slab) the tiles_n blocks that share an M-tile
   // split the work by K-tile (K-tile k goes to column tile k % tiles_n) and each writes its own
   // partial row [split * tiles_n + tn], so no block is slower than the others; without one, the
   // first column tile's blocks do it all (a.cs += directly).
   const bool cs_split = a.cs_slab != nullptr;
-  const bool do_cs = a.cs != nullptr && (cs_split || tn == 0);
+  const bool do_cs = CS && a.cs != nullptr && (cs_split || tn == 0);
   float cs0 = 0.f, cs1 = 0.f;
-  // the summed fragment is the MFMA's own A fragment fa[I0 + wc] of the phase (no extra LDS read
+  // the summed fragment is the MFMA's own A fragment fa[I0] of the phase (no extra LDS read
   // or register: a separate transposed read of it held 4 more VGPRs in a kernel at 256)
-  auto cs_add = [&](float& dst, const bf16x8_t& f) {
+  // on: all ones in the K-tiles this block sums, else 0 (the sum then adds +0.0, which leaves dst
+  // as it is: dst starts at +0.0 and never becomes -0.0), so the burst has no branch in it
+  auto cs_add = [&](float& dst, const bf16x8_t& f, uint32_t on) {
     typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
     const u32x4 u = __builtin_bit_cast(u32x4, f);
-    float t = 0.f;
+    // (the chain starts at the first pair, not at 0: that differs only when every term is -0.0,
+    // and then only in the sign of a zero that is added to dst, which is never -0.0)
+    float t = __uint_as_float(u[0] << 16) + __uint_as_float(u[0] & 0xFFFF0000u);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) t += __uint_as_float(u[e] << 16) + __uint_as_float(u[e] & 0xFFFF0000u);
-    dst += t;
+    for (int e = 1; e < 4; ++e) t += __uint_as_float(u[e] << 16) + __uint_as_float(u[e] & 0xFFFF0000u);
+    dst += __uint_as_float(__float_as_uint(t) & on);
   };
 
   stage(0, 0); stage(0, 1); stage(0, 2); stage(0, 3);
@@ -811,6 +831,10 @@ __global__ __launch_bounds__(512, 1) void gemm256_tn_kernel(GemmArgs a, int tile
   __builtin_amdgcn_s_barrier();
   if (wr) __builtin_amdgcn_s_barrier();  // stagger: waves 4-7 one barrier behind
 
+#define TN_MFMAS(I0)                                                                    \
+  _Pragma("unroll") for (int i = I0; i < I0 + 4; ++i)                                   \
+  _Pragma("unroll") for (int j = 0; j < 4; ++j)                                         \
+      acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
 #define TN_PHASE(READS, STAGE, VMWAIT, I0, KS)                                          \
   READS;                                                                                \
   STAGE;                                                                                \
@@ -818,27 +842,35 @@ __global__ __launch_bounds__(512, 1) void gemm256_tn_kernel(GemmArgs a, int tile
   if (VMWAIT) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                          \
   __builtin_amdgcn_s_barrier();                                                         \
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                    \
-  if (do_cs && my_k) {  /* wave-uniform wc: a scalar branch, static fragment indices; */ \
-    /* summed before the MFMAs so that no fragment outlives them */                       \
-    if (wc == 0) cs_add((I0) ? cs1 : cs0, fa[(I0) + 0]);                                  \
-    else if (wc == 1) cs_add((I0) ? cs1 : cs0, fa[(I0) + 1]);                             \
-    else if (wc == 2) cs_add((I0) ? cs1 : cs0, fa[(I0) + 2]);                             \
-    else cs_add((I0) ? cs1 : cs0, fa[(I0) + 3]);                                          \
-  }                                                                                       \
   __builtin_amdgcn_sched_barrier(0);                                                    \
   __builtin_amdgcn_s_setprio(1);                                                        \
-  _Pragma("unroll") for (int i = I0; i < I0 + 4; ++i)                                   \
-  _Pragma("unroll") for (int j = 0; j < 4; ++j)                                         \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0); \
+  /* CS: the sums of the phase's own first fragment, issued between the MFMAs that read it */ \
+  /* (two VALU after each of the first eight MFMAs), so the MFMA pipe never waits for them  */ \
+  /* and the fragment dies with its phase; one basic block (a branch around two copies of  */ \
+  /* the burst spilled 230 VGPRs)                                                          */ \
+  if (CS) cs_add((I0) ? cs1 : cs0, fa[I0], cs_on);                                        \
+  TN_MFMAS(I0)                                                                            \
+  if (CS) {                                                                               \
+    _Pragma("unroll") for (int p = 0; p < 9; ++p) {                                       \
+      __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);                                    \
+      __builtin_amdgcn_sched_group_barrier(0x2, 2, 0);                                    \
+    }                                                                                     \
+    __builtin_amdgcn_sched_group_barrier(0x8, 7, 0);                                      \
+  }                                                                                       \
   __builtin_amdgcn_s_setprio(0);                                                        \
   __builtin_amdgcn_sched_barrier(0);                                                    \
   __builtin_amdgcn_s_barrier();
 
+  int kmod = 0;
   for (int s = 0; s < (nk >> 1); ++s) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int buf = h * (2 * G_LDA_HALF);
-      const bool my_k = !cs_split || (2 * s + h) % tiles_n == tn;  // block-uniform
+      // block-uniform, and computed without a branch (the loop body stays one basic block, so
+      // nothing of a phase can be sunk past it): this block sums the bias columns of K-tile
+      // 2 s + h when kmod = (2 s + h) % tiles_n is its column tile
+      const uint32_t cs_on = (uint32_t)(do_cs & (!cs_split | (kmod == tn))) ? ~0u : 0u;
+      kmod = kmod + 1 == tiles_n ? 0 : kmod + 1;
       // phase 1 (5): ks0, i 0-3
       TN_PHASE(
           { _Pragma("unroll") for (int i = 0; i < 4; ++i) fa[i] = frag(buf + fA[i]);
@@ -858,8 +890,20 @@ __global__ __launch_bounds__(512, 1) void gemm256_tn_kernel(GemmArgs a, int tile
     }
   }
 #undef TN_PHASE
+#undef TN_MFMAS
   if (!wr) __builtin_amdgcn_s_barrier();  // balance the stagger
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+
+  // the epilogue's lane coordinates from a lane index read here (volatile asm): derived from the
+  // one read at kernel start they were hoisted above the K-loop and held registers through it
+  // (two of them spilled in the bias variant)
+  int g, ii;
+  {
+    uint32_t ln;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+    g = (int)(ln >> 4);
+    ii = (int)(ln & 15);
+  }
 
   if (do_cs) {
     cs0 += __shfl_xor(cs0, 16, 64);
@@ -888,14 +932,14 @@ __global__ __launch_bounds__(512, 1) void gemm256_tn_kernel(GemmArgs a, int tile
     for (int i = 0; i < 8; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int m = m0 + wr * 128 + i * 16 + ii;
+        const int m = m0 + wr * 128 + ti(i) * 16 + ii;
         const int n = n0 + wc * 64 + j * 16 + 4 * g;
         if (m < a.M && n < a.N)  // N % 8 == 0: n .. n + 3 in range
           *reinterpret_cast<f32x4*>(C + (int64_t)m * ldc + n) = acc[i][j];
       }
   } else {
     auto ld = [&](int i, int j) {
-      const int m = m0 + wr * 128 + i * 16 + ii;
+      const int m = m0 + wr * 128 + ti(i) * 16 + ii;
       const int n = n0 + wc * 64 + j * 16 + 4 * g;
       return (m < a.M && n < a.N) ? *reinterpret_cast<const f32x4*>(C + (int64_t)m * ldc + n)
                                   : (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -912,7 +956,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_tn_kernel(GemmArgs a, int tile
       asm volatile("" ::"v"(cin[i & 1][0]), "v"(cin[i & 1][1]), "v"(cin[i & 1][2]), "v"(cin[i & 1][3]));
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int m = m0 + wr * 128 + i * 16 + ii;
+        const int m = m0 + wr * 128 + ti(i) * 16 + ii;
         const int n = n0 + wc * 64 + j * 16 + 4 * g;
         if (m < a.M && n < a.N)
           *reinterpret_cast<f32x4*>(C + (int64_t)m * ldc + n) = acc[i][j] + cin[i & 1][j];
@@ -1437,7 +1481,10 @@ bool mmseq_gemm256_tn(const GemmArgs& a, hipStream_t s, hipError_t* err) {
     return false;
   const int tn = (a.N + 255) / 256;
   const int ntiles = ((a.M + 255) / 256) * tn;
-  hipLaunchKernelGGL(gemm256_tn_kernel, dim3(ntiles * a.splitk), dim3(512), 0, s, a, tn, ntiles);
+  if (a.cs)
+    hipLaunchKernelGGL(gemm256_tn_kernel<true>, dim3(ntiles * a.splitk), dim3(512), 0, s, a, tn, ntiles);
+  else
+    hipLaunchKernelGGL(gemm256_tn_kernel<false>, dim3(ntiles * a.splitk), dim3(512), 0, s, a, tn, ntiles);
   *err = hipGetLastError();
   return true;
 }
