@@ -480,6 +480,59 @@ mmseq_status mmseq_lstm_cell_bwd(int B, int H, const float* act, const float* c,
                                  float* dgates, float* dc_prev, mmseq_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Beam-search ordering of B stories at once (modeling_bert.py:1368-1402 BertForOrdering.step,
+ * :1411-1552 beam_search_pointer, generator.py:8-38 Beam), the beam state resident on the device:
+ * one call enqueues the whole decode on `stream`; between enqueue and result it neither
+ * synchronises with the host nor copies anything to it. fp32 throughout. Per story, T = N:
+ *   start    one candidate [] with score 0, (h, c) = (h0, c0), x = 0, nothing pointed, valid = W
+ *   step t   (t = 0 .. T-2) for t >= 1 every live candidate takes x = doc[last] and marks `last`
+ *            as pointed; LSTM cell (gates i, f, g, o, both biases); q = query_linear(h')
+ *   keys[j]  = pw_k(cat[hist[l1][j], hist[l2][j], forw[j], back[j]]), l1 / l2 the last / second-
+ *            to-last pick, their blocks zero while they do not exist (t = 0; t <= 1 for l2);
+ *            R[i][j] = hist[i][j] where i != j and neither is pointed, else 0;
+ *            forw[i] = sum_j R[i][j] / T, back[j] = sum_i R[i][j] / T
+ *   e[j]     = tanh_linear(tanh(q + keys[j] + okey[j])), -1e9 where j is pointed;
+ *            logp = log_softmax_j(e)
+ *   select   s[w][j] = score[w] - logp[w][j] over the nb live candidates, flat index w*T + j; the
+ *            k = min(valid, nb*T) smallest by (s, flat index) are chosen, ties to the lowest flat
+ *            index; pointed entries take part with their ~1e9 score and are chosen when k exceeds
+ *            the unpointed count (N = 3 with W = 16). A chosen entry is candidate w + [j] with
+ *            its parent's (h', c'); those of length T-1 are finished hypotheses (which happens in
+ *            step T-2 only, so valid stays W until then), the others the next beam in selection
+ *            order
+ *   result   order[b] = the finished hypothesis with the smallest score (the first selected on
+ *            ties) followed by the smallest index it does not contain; score[b] = its score.
+ *            N = 1 gives order [0] and score 0; N = 2 takes a single step.
+ * pw_k is linear, so its four input blocks are projected once per story and keys[j] is a sum of
+ * projected rows: fp32 sums in another order than the reference's one dot product per key.
+ * Supported: 1 <= N <= 16, 1 <= W <= 32, any H with 16 H < 2^30, any B with 2048 B < 2^30; anything else
+ * returns MMSEQ_EUNSUPPORTED before anything is launched (as does MMSEQ_EINVAL for a null
+ * buffer or a short / unaligned workspace).
+ *   doc, okey [B][N][H]   encode()[0] (sentence vectors), encode()[3] (key_linear output)
+ *   hist      [B][N][N][H+2] = cat(cls_mat, softmax(cs_mat)), rows contiguous
+ *   h0, c0    [B][H]      encode()[2]
+ *   w_ih, w_hh [4H][H], b_ih, b_hh [4H]   decoder.{weight,bias}_{ih,hh}_l0
+ *   w_q [H][H], b_q [H]   query_linear;   w_pw [H][4(H+2)]  pw_k.weight (no bias)
+ *   w_t [H], b_t [1]      tanh_linear     (all weights [out][in] as the head's store holds them)
+ *   order [B][N] int64, score [B] f32     outputs
+ *   workspace: mmseq_beam_workspace(B, N, H, W) bytes (0 for an unsupported shape), 16-byte
+ *     aligned, contents irrelevant on entry: rows of beam slots that are not live are computed
+ *     by the GEMMs but never read by another row, so nothing in it, NaN included, reaches a
+ *     result. Two calls on the same inputs give bit-identical outputs.
+ * Every step reuses the workspace and reads what the step before it wrote there, so the call's
+ * work is ordered on `stream` only: a concurrent call on another stream needs its own workspace
+ * and outputs, and the inputs must stay unchanged until the work enqueued here has run.
+ * ------------------------------------------------------------------------------------------ */
+int64_t mmseq_beam_workspace(int B, int N, int H, int W);
+mmseq_status mmseq_beam_search(int B, int N, int H, int W, const float* doc, const float* okey,
+                               const float* hist, const float* h0, const float* c0,
+                               const float* w_ih, const float* b_ih, const float* w_hh,
+                               const float* b_hh, const float* w_q, const float* b_q,
+                               const float* w_pw, const float* w_t, const float* b_t,
+                               int64_t* order, float* score, void* workspace,
+                               int64_t workspace_bytes, mmseq_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * MX-fp8 forward GEMMs (BASELINE config 5 "fp8 MFMA"; v_mfma_scale_f32_16x16x128_f8f6f4).
  *  Format: OCP e4m3 elements, one E8M0 scale (2^(s-127)) per 32 consecutive K-elements of a row
  *  (OCP MX: s = floor(log2 amax) - 8 + 127, elements = x / 2^(s-127) clamped to +-448, RNE).

@@ -154,6 +154,8 @@ _SIGS = {
                           [_vp] * 4),
     "mmseq_lstm_cell_fwd": (ctypes.c_int, [ctypes.c_int] * 2 + [_vp, _c_i64] + [_vp] * 6),
     "mmseq_lstm_cell_bwd": (ctypes.c_int, [ctypes.c_int] * 2 + [_vp] * 8),
+    "mmseq_beam_workspace": (ctypes.c_int64, [ctypes.c_int] * 4),
+    "mmseq_beam_search": (ctypes.c_int, [ctypes.c_int] * 4 + [_vp] * 17 + [_c_i64, _vp]),
     "mmseq_mxfp8_scale_bytes": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int]),
     "mmseq_quant_mxfp8": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _c_i64, ctypes.c_int,
                                          _vp, _c_i64, _vp, _vp]),
@@ -613,6 +615,44 @@ def lstm_cell_bwd(act, c, c_out, dh, dc_next, dgates, dc_prev):
                                      _p(dh) if dh is not None else None,
                                      _p(dc_next) if dc_next is not None else None, _p(dgates),
                                      _p(dc_prev), _stream()), "mmseq_lstm_cell_bwd")
+
+
+EUNSUPPORTED = -2
+
+
+def beam_workspace(B, N, H, W):
+    """Bytes of workspace mmseq_beam_search needs; 0 where the shape is unsupported."""
+    return int(lib().mmseq_beam_workspace(B, N, H, W))
+
+
+def beam_search(doc, okey, hist, h0, c0, weights, W, order, score, workspace):
+    """mmseq_beam_search: doc / okey [B][N][H], hist [B][N][N][H+2], h0 / c0 [B][H] (f32,
+    contiguous); weights = (w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t) in the head store's
+    [out][in] layouts; order int64 [B][N], score f32 [B]; workspace: a uint8 / f32 device tensor
+    of at least beam_workspace(B, N, H, W) bytes. Returns the status for MMSEQ_EUNSUPPORTED (the
+    caller decides what to do instead) and raises on every other failure."""
+    B, N, H = doc.shape
+    w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t = weights
+    shapes = ((doc, (B, N, H)), (okey, (B, N, H)), (hist, (B, N, N, H + 2)), (h0, (B, H)),
+              (c0, (B, H)), (w_ih, (4 * H, H)), (b_ih, (4 * H,)), (w_hh, (4 * H, H)),
+              (b_hh, (4 * H,)), (w_q, (H, H)), (b_q, (H,)), (w_pw, (H, 4 * (H + 2))), (score, (B,)))
+    _dev(order, workspace, *(t for t, _ in shapes), w_t, b_t)
+    for t, shp in shapes:
+        if t.dtype != torch.float32 or tuple(t.shape) != shp or not t.is_contiguous():
+            raise ValueError(f"beam_search: contiguous f32 {shp} expected, got {tuple(t.shape)} "
+                             f"{t.dtype}")
+    for t, n in ((w_t, H), (b_t, 1)):
+        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
+            raise ValueError("beam_search: tanh_linear weight [H] / bias [1] f32 expected")
+    if order.dtype != torch.int64 or tuple(order.shape) != (B, N) or not order.is_contiguous():
+        raise ValueError("beam_search: order must be contiguous int64 [B][N]")
+    st = lib().mmseq_beam_search(B, N, H, int(W), _p(doc), _p(okey), _p(hist), _p(h0), _p(c0),
+                                 _p(w_ih), _p(b_ih), _p(w_hh), _p(b_hh), _p(w_q), _p(b_q),
+                                 _p(w_pw), _p(w_t), _p(b_t), _p(order), _p(score), _p(workspace),
+                                 workspace.numel() * workspace.element_size(), _stream())
+    if st != EUNSUPPORTED:
+        _check(st, "mmseq_beam_search")
+    return st
 
 
 class MXFP8:

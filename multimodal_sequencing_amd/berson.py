@@ -19,6 +19,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from . import _native as N_
 from . import kernels as K
 from .checkpoint import JsonConfigMixin, berson_from_pretrained, save_pretrained
 from .params import ParamStore, Spec, attach_tree, linear_specs, ln_specs, normal, uniform, zeros
@@ -334,19 +335,27 @@ def beam_search_pointer(args, model, input_ids, attention_mask=None, token_type_
                         head_mask=None, images=None):
     """:1411-1552 + generator.py Beam (B = 1). Ties in the k-smallest selection break toward the
     lowest flat index (deterministic); returns the ordering as a list of ints."""
-    (sent, _p, dec_init, okeys, _cls, cls_mat, _cs, cs_mat, _h1, _h2) = model.encode(
+    enc = model.encode(
         input_ids, attention_mask, token_type_ids, pairs_list, passage_length, pairs_num,
         sep_positions, ground_truth, mask_cls, pairwise_labels, cuda, head_mask, images)
-    T = int(mask_cls.shape[1])
-    doc = sent[0]
+    return _beam_decode_story(args, model, enc, 0)[0]
+
+
+@torch.no_grad()
+def _beam_decode_story(args, model, enc, b):
+    """The host-driven beam search over story b of an encode() tuple -> (order, best score)."""
+    (sent, _p, dec_init, okeys, _cls, cls_mat, _cs, cs_mat, _h1, _h2) = enc
+    T = int(sent.shape[1])
+    doc = sent[b]
+    okeys = okeys[b:b + 1]
     H = doc.shape[-1]
     dev = doc.device
-    rela = torch.cat([cls_mat, torch.softmax(cs_mat, -1)], -1)
+    rela = torch.cat([cls_mat[b:b + 1], torch.softmax(cs_mat[b:b + 1], -1)], -1)
     hist = rela.clone()
     W = getattr(args, "beam_size", 16)
     cands, scores, hyps = [[]], [0.0], []
     valid = W
-    h, c = dec_init[0][0], dec_init[1][0]
+    h, c = dec_init[0][0][b:b + 1], dec_init[1][0][b:b + 1]
     rela_mask = (1 - torch.eye(T, dtype=torch.int64, device=dev))[None]
     pointed = torch.zeros(1, T, dtype=torch.int64, device=dev)
     x = torch.zeros(1, H, device=dev)
@@ -387,8 +396,58 @@ def beam_search_pointer(args, model, input_ids, attention_mask=None, token_type_
         h, c = h[ri], c[ri]
         pointed, rela_mask, rela, hist = pointed[ri], rela_mask[ri], rela[ri], hist[ri]
         cands, scores = new_c, new_s
-    best = sorted(hyps, key=lambda z: z[1])[0][0]
-    return best + sorted(set(range(T)) - set(best))[:1]
+    best, best_score = sorted(hyps, key=lambda z: z[1])[0]
+    return best + sorted(set(range(T)) - set(best))[:1], best_score
+
+
+_BEAM_WEIGHTS = ("decoder.weight_ih_l0", "decoder.bias_ih_l0", "decoder.weight_hh_l0",
+                 "decoder.bias_hh_l0", "query_linear.weight", "query_linear.bias", "pw_k.weight",
+                 "tanh_linear.weight", "tanh_linear.bias")
+
+
+@torch.no_grad()
+def beam_decode_batch(args, model, enc):
+    """Every story of an encode() tuple through ONE mmseq_beam_search (the beam state stays on
+    the device, nothing synchronises until the caller reads the result) -> (order int64 [B][N],
+    best score f32 [B]) on the device. Where the ABI reports the shape unsupported, the stories
+    go through the per-story decoder one by one."""
+    (sent, _p, dec_init, okeys, _cls, cls_mat, _cs, cs_mat, _h1, _h2) = enc
+    B, N, H = sent.shape
+    W = int(getattr(args, "beam_size", 16))
+    dev = sent.device
+    order = torch.empty(B, N, dtype=torch.int64, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    nbytes = N_.beam_workspace(B, N, H, W)
+    st = N_.EUNSUPPORTED
+    if nbytes > 0:
+        cache = model.__dict__.setdefault("_beam_ws", {})
+        ws = cache.get((B, N, H, W))
+        if ws is None:
+            ws = cache[(B, N, H, W)] = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        hist = torch.cat([cls_mat, torch.softmax(cs_mat, -1)], -1).contiguous()
+        st = N_.beam_search(sent.contiguous(), okeys.contiguous(), hist,
+                            dec_init[0][0].contiguous(), dec_init[1][0].contiguous(),
+                            [model.store.f32(n) for n in _BEAM_WEIGHTS], W, order, score, ws)
+    if st == N_.EUNSUPPORTED:
+        res = [_beam_decode_story(args, model, enc, b) for b in range(B)]
+        order = torch.tensor([r[0] for r in res], dtype=torch.int64, device=dev)
+        score = torch.tensor([r[1] for r in res], dtype=torch.float32, device=dev)
+    return order, score
+
+
+@torch.no_grad()
+def beam_search_pointer_batch(args, model, input_ids, attention_mask=None, token_type_ids=None,
+                              pairs_list=None, passage_length=None, pairs_num=None,
+                              sep_positions=None, ground_truth=None, mask_cls=None,
+                              pairwise_labels=None, cuda=None, head_mask=None, images=None):
+    """beam_search_pointer for B >= 1 stories: one encode at the batched shape, one device-resident
+    decode, one device-to-host copy of the orders -> list of B orderings. The best hypotheses'
+    scores stay on the device in `model.last_beam_scores` ([B] f32)."""
+    enc = model.encode(
+        input_ids, attention_mask, token_type_ids, pairs_list, passage_length, pairs_num,
+        sep_positions, ground_truth, mask_cls, pairwise_labels, cuda, head_mask, images)
+    order, model.last_beam_scores = beam_decode_batch(args, model, enc)
+    return order.tolist()
 
 
 def berson_pointer_network(args, model, tokenizer, inputs):
@@ -400,3 +459,15 @@ def berson_pointer_network(args, model, tokenizer, inputs):
         images = images.to(model.device_, torch.float32).contiguous()
     berson["images"] = images
     return beam_search_pointer(args, model, **berson)
+
+
+def berson_pointer_network_batch(args, model, tokenizer, inputs):
+    """Ordering indices for the B >= 1 stories of `inputs` (same keys as berson_pointer_network)
+    -> list of B lists."""
+    berson = prepare_berson_inputs(inputs["input_ids"], inputs["labels"], model.n_steps,
+                                   device=model.device_)
+    images = inputs.get("images")
+    if images is not None:
+        images = images.to(model.device_, torch.float32).contiguous()
+    berson["images"] = images
+    return beam_search_pointer_batch(args, model, **berson)

@@ -1,0 +1,299 @@
+// Batched beam-search ordering (modeling_bert.py:1368-1402 BertForOrdering.step, :1411-1552
+// beam_search_pointer, generator.py:8-38 Beam) for B stories at once, beam state resident on the
+// device: the whole decode is enqueued on one stream, with no host synchronisation and no copy to
+// the host between enqueue and result (the per-story path does N - 1 round trips per story).
+//
+// Every story holds W fixed beam slots. All candidates of a story have the same length t at step
+// t, so hypotheses finish only in the last step (t = N - 2), `valid` stays W until then, and the
+// live count nb(t) = min(W, nb(t-1) * N), nb(0) = 1 is the same for every story and known on the
+// host. The dense parts run over all B*W rows through mmseq_gemm; rows of slots >= nb hold
+// whatever the workspace held and are never read by another row.
+//
+// pw_k is linear, so the four blocks of its input are projected ONCE per story:
+//   PROJ[g][b][i][j][:] = pw_k.weight[:, g(H+2):(g+1)(H+2)] hist[b][i][j]        g = 0..3
+//   keys[j] = PROJ[0][l1][j] + PROJ[1][l2][j] + (sum_{j'} m PROJ[2][j][j']) / N
+//                                             + (sum_{i}  m PROJ[3][i][j]) / N
+// with m = (i != j, neither pointed). Likewise x W_ih^T + b_ih for x = doc[b][i] is one GEMM.
+#include "common.h"
+
+namespace {
+
+constexpr int BEAM_MAXN = 16;
+constexpr int BEAM_MAXW = 32;
+
+struct BeamWs {  // float offsets into the workspace, each a multiple of 4 (16-byte rows)
+  int64_t gx, proj, h[2], c[2], gh, q, s, score[2], seq[2], total;
+};
+
+inline int64_t up4(int64_t n) { return (n + 3) / 4 * 4; }
+
+BeamWs beam_layout(int B, int N, int H, int W) {
+  BeamWs w;
+  const int64_t R = (int64_t)B * W;
+  int64_t o = 0;
+  w.gx = o; o += up4((int64_t)B * N * 4 * H);
+  w.proj = o; o += 4 * up4((int64_t)B * N * N * H);
+  for (int i = 0; i < 2; ++i) { w.h[i] = o; o += up4(R * H); }
+  for (int i = 0; i < 2; ++i) { w.c[i] = o; o += up4(R * H); }
+  w.gh = o; o += up4(R * 4 * H);
+  w.q = o; o += up4(R * H);
+  w.s = o; o += up4(R * N);
+  for (int i = 0; i < 2; ++i) { w.score[i] = o; o += up4(R); }
+  for (int i = 0; i < 2; ++i) { w.seq[i] = o; o += up4(R * BEAM_MAXN); }  // int32 picks
+  w.total = o;
+  return w;
+}
+
+// slot 0 of every story <- (h0, c0), score 0; N == 1: the order is [0]
+__global__ __launch_bounds__(256) void beam_init_kernel(int N, int H, int W,
+                                                        const float* __restrict__ h0,
+                                                        const float* __restrict__ c0,
+                                                        float* __restrict__ h, float* __restrict__ c,
+                                                        float* __restrict__ score,
+                                                        int64_t* __restrict__ order,
+                                                        float* __restrict__ best) {
+  const int b = blockIdx.x;
+  if (N == 1) {
+    if (threadIdx.x == 0) { order[b] = 0; best[b] = 0.f; }
+    return;
+  }
+  const int64_t slot = (int64_t)b * W;
+  for (int u = threadIdx.x; u < H; u += 256) {
+    h[slot * H + u] = h0[(int64_t)b * H + u];
+    c[slot * H + u] = c0[(int64_t)b * H + u];
+  }
+  if (threadIdx.x == 0) score[slot] = 0.f;
+}
+
+__device__ __forceinline__ float bsigm(float x) { return 1.f / (1.f + expf(-x)); }
+
+// LSTM cell (gates i, f, g, o) of the live slots, in place: x W_ih^T + b_ih is row `last` of the
+// story's GX (t > 0) or b_ih alone (t = 0, x = 0); gh already holds h W_hh^T + b_hh.
+__global__ __launch_bounds__(256) void beam_cell_kernel(int H, int W, int N, int t, int nb,
+                                                        const float* __restrict__ gx,
+                                                        const float* __restrict__ b_ih,
+                                                        const float* __restrict__ gh,
+                                                        const int* __restrict__ seq,
+                                                        float* __restrict__ h, float* __restrict__ c) {
+  const int64_t slot = blockIdx.x;
+  const int b = (int)(slot / W), w = (int)(slot % W);
+  if (w >= nb) return;
+  const float* x = t > 0 ? gx + ((int64_t)b * N + seq[slot * BEAM_MAXN + t - 1]) * 4 * H : b_ih;
+  const float* g4 = gh + slot * 4 * H;
+  for (int u = threadIdx.x; u < H; u += 256) {
+    const float i = bsigm(x[u] + g4[u]);
+    const float f = bsigm(x[H + u] + g4[H + u]);
+    const float g = tanhf(x[2 * H + u] + g4[2 * H + u]);
+    const float o = bsigm(x[3 * H + u] + g4[3 * H + u]);
+    const float c2 = f * c[slot * H + u] + i * g;
+    c[slot * H + u] = c2;
+    h[slot * H + u] = o * tanhf(c2);
+  }
+}
+
+// One workgroup per live slot: e[j] = tanh_linear(tanh(q + keys[j] + okey[j])), -1e9 where
+// pointed, s[slot][j] = score[slot] - log_softmax(e)[j]. One wave per j, fixed summation order.
+__global__ __launch_bounds__(256) void beam_score_kernel(int N, int H, int W, int t, int nb,
+                                                         const float* __restrict__ q,
+                                                         const float* __restrict__ proj,
+                                                         int64_t proj_stride,
+                                                         const float* __restrict__ okey,
+                                                         const float* __restrict__ wt,
+                                                         const float* __restrict__ bt,
+                                                         const int* __restrict__ seq,
+                                                         const float* __restrict__ score,
+                                                         float* __restrict__ s) {
+  __shared__ float e[BEAM_MAXN];
+  const int64_t slot = blockIdx.x;
+  const int b = (int)(slot / W), w = (int)(slot % W);
+  if (w >= nb) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned pointed = 0;
+  for (int p = 0; p < t; ++p) pointed |= 1u << seq[slot * BEAM_MAXN + p];
+  const int l1 = t > 0 ? seq[slot * BEAM_MAXN + t - 1] : 0;
+  const int l2 = t > 1 ? seq[slot * BEAM_MAXN + t - 2] : 0;
+  const float* P1 = proj;
+  const float* P2 = proj + proj_stride;
+  const float* PF = proj + 2 * proj_stride;
+  const float* PB = proj + 3 * proj_stride;
+  const int64_t sb = (int64_t)b * N;  // story's first hist row block
+  const float* qr = q + slot * H;
+  const float fN = (float)N;  // both means divide by T (:1061-1062)
+  for (int j = wave; j < N; j += 4) {
+    const float* orow = okey + (sb + j) * H;
+    const bool jlive = !((pointed >> j) & 1u);
+    float acc = 0.f;
+    for (int u = lane; u < H; u += 64) {
+      float key = 0.f;
+      if (t > 0) key += P1[((sb + l1) * N + j) * H + u];
+      if (t > 1) key += P2[((sb + l2) * N + j) * H + u];
+      if (jlive) {
+        float f = 0.f, bk = 0.f;
+        for (int i = 0; i < N; ++i) {
+          if (i == j || ((pointed >> i) & 1u)) continue;
+          f += PF[((sb + j) * N + i) * H + u];
+          bk += PB[((sb + i) * N + j) * H + u];
+        }
+        key += f / fN;
+        key += bk / fN;
+      }
+      acc += wt[u] * tanhf(qr[u] + key + orow[u]);
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) e[j] = jlive ? acc + bt[0] : -1e9f;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float mx = -INFINITY;
+    for (int j = 0; j < N; ++j) mx = fmaxf(mx, e[j]);
+    float sum = 0.f;
+    for (int j = 0; j < N; ++j) sum += expf(e[j] - mx);
+    const float ls = logf(sum), sc = score[slot];
+    for (int j = 0; j < N; ++j) s[slot * N + j] = sc - ((e[j] - mx) - ls);
+  }
+}
+
+// One workgroup per story: the k smallest of the nb*N flat scores by (score, flat index) through
+// a rank count in LDS (no sort, no dynamically indexed registers), the chosen entries become
+// slots 0..k-1 of the next step in selection order with their parents' h', c'. In the last step
+// the first selected entry is the story's best hypothesis.
+__global__ __launch_bounds__(256) void beam_select_kernel(int N, int H, int W, int t, int nb, int k,
+                                                          int last, const float* __restrict__ s,
+                                                          const int* __restrict__ seq_cur,
+                                                          int* __restrict__ seq_nxt,
+                                                          float* __restrict__ score_nxt,
+                                                          const float* __restrict__ h_cur,
+                                                          const float* __restrict__ c_cur,
+                                                          float* __restrict__ h_nxt,
+                                                          float* __restrict__ c_nxt,
+                                                          int64_t* __restrict__ order,
+                                                          float* __restrict__ best) {
+  __shared__ float sh_s[BEAM_MAXW * BEAM_MAXN];
+  __shared__ int sh_sel[BEAM_MAXW];
+  __shared__ int sh_par[BEAM_MAXW];
+  const int b = blockIdx.x, n = nb * N;
+  const int64_t slot0 = (int64_t)b * W;
+  for (int i = threadIdx.x; i < n; i += 256) sh_s[i] = s[slot0 * N + i];
+  if (threadIdx.x < BEAM_MAXW) { sh_sel[threadIdx.x] = 0; sh_par[threadIdx.x] = 0; }
+  __syncthreads();
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const float v = sh_s[i];
+    int rank = 0;
+    for (int o = 0; o < n; ++o) {
+      const float x = sh_s[o];
+      rank += (x < v || (x == v && o < i)) ? 1 : 0;
+    }
+    if (rank < k) sh_sel[rank] = i;
+  }
+  __syncthreads();
+  if (last) {
+    if (threadIdx.x == 0) {
+      const int i = sh_sel[0], w = i / N, j = i % N;
+      unsigned have = 1u << j;
+      for (int p = 0; p < t; ++p) {
+        const int v = seq_cur[(slot0 + w) * BEAM_MAXN + p];
+        order[(int64_t)b * N + p] = v;
+        have |= 1u << v;
+      }
+      order[(int64_t)b * N + t] = j;
+      int miss = 0;
+      while ((have >> miss) & 1u) ++miss;  // length N - 1 < N entries: one index is always free
+      order[(int64_t)b * N + t + 1] = miss;
+      best[b] = sh_s[i];
+    }
+    return;
+  }
+  if (threadIdx.x < k) {
+    const int r = threadIdx.x, i = sh_sel[r], w = i / N, j = i % N;
+    for (int p = 0; p < t; ++p)
+      seq_nxt[(slot0 + r) * BEAM_MAXN + p] = seq_cur[(slot0 + w) * BEAM_MAXN + p];
+    seq_nxt[(slot0 + r) * BEAM_MAXN + t] = j;
+    score_nxt[slot0 + r] = sh_s[i];
+    sh_par[r] = w;
+  }
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < k * H; idx += 256) {
+    const int r = idx / H, u = idx - r * H;
+    const int64_t src = (slot0 + sh_par[r]) * H + u, dst = (slot0 + r) * H + u;
+    h_nxt[dst] = h_cur[src];
+    c_nxt[dst] = c_cur[src];
+  }
+}
+
+inline bool beam_supported(int B, int N, int H, int W) {
+  return B >= 0 && N >= 1 && N <= BEAM_MAXN && W >= 1 && W <= BEAM_MAXW && H >= 1 &&
+         (int64_t)B * BEAM_MAXW * BEAM_MAXN * 4 < INT32_MAX / 2 && (int64_t)H * 4 * 4 < INT32_MAX / 2;
+}
+
+}  // namespace
+
+extern "C" int64_t mmseq_beam_workspace(int B, int N, int H, int W) {
+  if (!beam_supported(B, N, H, W)) return 0;
+  return beam_layout(B, N, H, W).total * 4;
+}
+
+extern "C" mmseq_status mmseq_beam_search(int B, int N, int H, int W, const float* doc,
+                                          const float* okey, const float* hist, const float* h0,
+                                          const float* c0, const float* w_ih, const float* b_ih,
+                                          const float* w_hh, const float* b_hh, const float* w_q,
+                                          const float* b_q, const float* w_pw, const float* w_t,
+                                          const float* b_t, int64_t* order, float* score,
+                                          void* workspace, int64_t workspace_bytes,
+                                          mmseq_stream stream) {
+  if (!beam_supported(B, N, H, W))
+    return mmseq_set_error(MMSEQ_EUNSUPPORTED,
+                           "beam_search: B=%d N=%d H=%d W=%d outside 1 <= N <= %d, 1 <= W <= %d "
+                           "(or B*W*N / H too large for 32-bit row counts)",
+                           B, N, H, W, BEAM_MAXN, BEAM_MAXW);
+  MMSEQ_REQUIRE(doc && okey && hist && h0 && c0 && w_ih && b_ih && w_hh && b_hh && w_q && b_q &&
+                    w_pw && w_t && b_t && order && score,
+                "beam_search: null buffer");
+  const BeamWs L = beam_layout(B, N, H, W);
+  MMSEQ_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= L.total * 4,
+                "beam_search: workspace must be 16-byte aligned and hold %lld bytes (got %lld)",
+                (long long)(L.total * 4), (long long)workspace_bytes);
+  if (B == 0) return MMSEQ_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  float* ws = reinterpret_cast<float*>(workspace);
+  const int R = B * W;
+  float* hb[2] = {ws + L.h[0], ws + L.h[1]};
+  float* cb[2] = {ws + L.c[0], ws + L.c[1]};
+  float* sc[2] = {ws + L.score[0], ws + L.score[1]};
+  int* sq[2] = {reinterpret_cast<int*>(ws + L.seq[0]), reinterpret_cast<int*>(ws + L.seq[1])};
+  hipLaunchKernelGGL(beam_init_kernel, dim3(B), dim3(256), 0, st, N, H, W, h0, c0, hb[0], cb[0],
+                     sc[0], order, score);
+  mmseq_status e = mmseq_check_launch("beam_init");
+  if (e != MMSEQ_OK || N == 1) return e;
+  auto gemm = [&](int M, int Nn, int K, const float* A, int64_t lda, const float* Bm, int64_t ldb,
+                  float* C, const float* bias) {
+    return mmseq_gemm(0, M, Nn, K, 1, A, lda, 0, Bm, ldb, 0, C, Nn, 0, bias, MMSEQ_ACT_NONE,
+                      nullptr, nullptr, nullptr, 0, 0, 1.0f, 0, MMSEQ_F32, MMSEQ_F32, nullptr,
+                      MMSEQ_GEMM_AUTO, nullptr, 0, stream);
+  };
+  // once per call: the input gates of every sentence and the four projections of hist
+  if (N > 2 && (e = gemm(B * N, 4 * H, H, doc, H, w_ih, H, ws + L.gx, b_ih)) != MMSEQ_OK) return e;
+  const int64_t pstride = up4((int64_t)B * N * N * H);
+  for (int g = 0; g < 4; ++g)
+    if ((e = gemm(B * N * N, H, H + 2, hist, H + 2, w_pw + (int64_t)g * (H + 2), 4 * (int64_t)(H + 2),
+                  ws + L.proj + g * pstride, nullptr)) != MMSEQ_OK)
+      return e;
+  int nb = 1;
+  for (int t = 0; t < N - 1; ++t) {
+    const int cur = t & 1, nxt = cur ^ 1, last = t == N - 2;
+    const int n = nb * N, k = W < n ? W : n;
+    if ((e = gemm(R, 4 * H, H, hb[cur], H, w_hh, H, ws + L.gh, b_hh)) != MMSEQ_OK) return e;
+    hipLaunchKernelGGL(beam_cell_kernel, dim3(R), dim3(256), 0, st, H, W, N, t, nb, ws + L.gx, b_ih,
+                       ws + L.gh, sq[cur], hb[cur], cb[cur]);
+    if ((e = mmseq_check_launch("beam_cell")) != MMSEQ_OK) return e;
+    if ((e = gemm(R, H, H, hb[cur], H, w_q, H, ws + L.q, b_q)) != MMSEQ_OK) return e;
+    hipLaunchKernelGGL(beam_score_kernel, dim3(R), dim3(256), 0, st, N, H, W, t, nb, ws + L.q,
+                       ws + L.proj, pstride, okey, w_t, b_t, sq[cur], sc[cur], ws + L.s);
+    if ((e = mmseq_check_launch("beam_score")) != MMSEQ_OK) return e;
+    hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(256), 0, st, N, H, W, t, nb, k, last,
+                       ws + L.s, sq[cur], sq[nxt], sc[nxt], hb[cur], cb[cur], hb[nxt], cb[nxt],
+                       order, score);
+    if ((e = mmseq_check_launch("beam_select")) != MMSEQ_OK) return e;
+    nb = k;
+  }
+  return MMSEQ_OK;
+}

@@ -4,7 +4,10 @@ and the ordering metrics (metrics.py).
 
 Same contract as the reference: one story per batch (SequentialSampler), the gold order is
 batch[3] (a [1, R, N] tensor is a multi-reference gold: its first row is used for decoding and
-pmr/acc, all rows for the metrics), a one-sentence story is "predicted" as its gold order; lines
+pmr/acc, all rows for the metrics), a one-sentence story is "predicted" as its gold order. With
+per_gpu_eval_batch_size > 1 (the reference supports 1 only) every loader batch is decoded at once
+by berson.berson_pointer_network_batch and story b of it uses batch[3][b] / batch[4][b]; files and
+metrics are those of a batch-size-1 run over the same stories. Lines
 'pred|||gold' go to output_order.txt; results {'acc_dev', 'pmr_dev', 'taus_dev'} are written to
 eval_results_split_{split}.txt and appended to all_eval_results.txt; with
 args.eval_save_all_results a per-story all_predictions.csv (pm, em, lcs_substr, lcs, ms, wms,
@@ -138,14 +141,54 @@ def _json_default(o):
     raise TypeError(type(o))
 
 
+def _evaluate_batched(args, model, loader, tokenizer, pointer_network_batch, f):
+    """The loop of berson_evaluate for loader batches of B >= 1 stories: one batched decode per
+    loader batch (the last, smaller one included), then per story what the one-story loop does.
+    max_eval_steps counts stories and stops after exactly that many."""
+    truth, predicted, guids = [], [], []
+    limit = getattr(args, "max_eval_steps", 0)
+    for batch in loader:
+        gold = batch[3]
+        B = gold.shape[0]
+        if limit > 0:
+            B = min(B, limit - len(truth))
+        multiref = gold.ndim > 2
+        labels = gold[:B, 0, :] if multiref else gold[:B]
+        if labels.shape[-1] == 1 and not multiref:  # one-sentence stories: the gold order
+            preds = labels.tolist()
+        else:
+            with torch.no_grad():
+                inputs = {"input_ids": batch[0][:B], "attention_mask": batch[1][:B],
+                          "labels": labels}
+                if getattr(args, "multimodal", False):
+                    inputs["images"] = batch[-1][:B]
+                    if getattr(args, "include_num_img_regional_features", False):
+                        inputs["img_regional_features"] = batch[-2][:B]
+                preds = pointer_network_batch(args, model, tokenizer, inputs)
+        for b in range(B):
+            truth.append(gold[b].tolist())
+            predicted.append(preds[b])
+            guids.append(str(batch[4][b]).split("###")[0])
+            print("{}|||{}".format(" ".join(map(str, preds[b])), " ".join(map(str, truth[-1]))),
+                  file=f)
+        if limit > 0 and len(truth) >= limit:
+            logger.info("Early stopping evaluation at step: %d", limit)
+            break
+    return truth, predicted, guids
+
+
 def berson_evaluate(args, model, load_and_cache_examples, tokenizer, prefix="",
-                    data_split="test", human_evaluate=False, pointer_network=None):
+                    data_split="test", human_evaluate=False, pointer_network=None,
+                    pointer_network_batch=None):
     """eval.py:39-187. `load_and_cache_examples(args, [task], tokenizer, evaluate=True,
     data_split=...)` returns a map-style dataset of tuples (input_ids, attention_mask,
     token_type_ids, labels, guid, ..., images); `pointer_network` defaults to the device beam
-    search berson.berson_pointer_network."""
+    search berson.berson_pointer_network, `pointer_network_batch` (used when the evaluation batch
+    size exceeds 1) to berson.berson_pointer_network_batch."""
     if pointer_network is None:
         from .berson import berson_pointer_network as pointer_network
+    if pointer_network_batch is None:
+        from .berson import berson_pointer_network_batch as pointer_network_batch
     from torch.utils.data import DataLoader, SequentialSampler
     results = {}
     tasks = args.task_names
@@ -163,6 +206,10 @@ def berson_evaluate(args, model, load_and_cache_examples, tokenizer, prefix="",
         multiref = False
         steps = 0
         model.eval()
+        if args.eval_batch_size > 1:
+            truth, predicted, guids = _evaluate_batched(args, model, loader, tokenizer,
+                                                        pointer_network_batch, f)
+            loader = ()  # all decoded: the one-story loop below has nothing left to do
         for batch in loader:
             tru = batch[3]
             if tru.ndim > 2:
