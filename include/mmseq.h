@@ -99,8 +99,11 @@ mmseq_status mmseq_gemm(int trans, int M, int N, int K, int batch,
                         float alpha, int accumulate, mmseq_dtype in_dtype, mmseq_dtype out_dtype,
                         const mmseq_dropout* drop, int variant, void* workspace,
                         int64_t workspace_bytes, mmseq_stream stream);
-/* Bytes of split-K workspace beyond which mmseq_gemm / mmseq_gemm_wgrad gain nothing for an
- * M x N x K problem on the current device. */
+/* Bytes of workspace beyond which mmseq_gemm / mmseq_gemm_wgrad change nothing for an M x N x K
+ * problem on the current device: the largest amount any of their split-K plans uses when nothing
+ * limits it, the wgrad's bias partial rows included (so also nonzero for a wgrad too short to
+ * split). A call given this much runs exactly as with any larger workspace; a call given less
+ * takes fewer splits or sums the bias gradient without partial rows. */
 int64_t mmseq_gemm_workspace_size(int M, int N, int K);
 /* Weight + bias gradient of a Linear in one pass (replaces the wgrad GEMM and the bias column sum
  * of every nn.Linear backward on the path): C[M][N] += sum_k A[k][m] B[k][n] (A = dY [K][lda],

@@ -937,19 +937,10 @@ __device__ __forceinline__ void attn_fwd_tail(const AttnArgs& a, unsigned short*
 template <int DMODE, bool WIDE, bool Q8 = false>  // dropout: 0 none, 1 counter hash, 2 counter
                                  // hash + keep bits out; WIDE: dropout pair indices >= 2^32 (64-bit
                                  // index arithmetic); Q8: MX-fp8 output (eval, the O-proj operand)
-#ifndef MMSEQ_ATTN_FAST_EXP
-#define MMSEQ_ATTN_FAST_EXP 1  // forward: no per-tile row max where the tile's row sums stay <= 2^8
-#endif
-#ifndef MMSEQ_ATTN_FWD_RECOMP
-#define MMSEQ_ATTN_FWD_RECOMP 0  // without dropout: lane-derived offsets recomputed per tile
-#endif
-#ifndef MMSEQ_ATTN_FWD_WPE
-#define MMSEQ_ATTN_FWD_WPE 4  // forward workgroups per CU the register budget is sized for
-#endif
-// (four everywhere but the 64-bit-index dropout forms: <= 128 VGPRs since the forward has no
-// per-tile row max and keeps scalar row sums, so the lane-derived LDS and DMA offsets are held
-// across the loop again, MMSEQ_ATTN_FWD_RECOMP 0: T = 393 forward -9 %)
-__global__ __launch_bounds__(256, DMODE == 0 ? 4 : (WIDE ? 3 : MMSEQ_ATTN_FWD_WPE)) void attn_fwd_bf16_kernel(AttnArgs a) {
+// (four workgroups per CU everywhere but the 64-bit-index dropout forms: <= 128 VGPRs since the
+// forward has no per-tile row max and keeps scalar row sums, so the lane-derived LDS and DMA offsets
+// are held across the loop rather than recomputed per tile: T = 393 forward -9 %)
+__global__ __launch_bounds__(256, DMODE != 0 && WIDE ? 3 : 4) void attn_fwd_bf16_kernel(AttnArgs a) {
   constexpr bool DROP = DMODE != 0;
   extern __shared__ __attribute__((aligned(16))) unsigned short smem[];  // 2 x (K, V) + bias
   float* sBias = reinterpret_cast<float*>(smem + 4 * IMG);
@@ -959,13 +950,11 @@ __global__ __launch_bounds__(256, DMODE == 0 ? 4 : (WIDE ? 3 : MMSEQ_ATTN_FWD_WP
   const int T = a.T;
   const BlkIdx bi = attn_block((a.Tq + 127) >> 7, a.heads);
   const int h = bi.h, p = bi.p;
-#ifndef MMSEQ_ATTN_NO_TAIL
   // the last 1-16 rows of T (bit-identical whether or not the launch covers only Tq < T rows)
   if (((T - 1) & 127) < 16 && bi.x == (T - 1) >> 7) {
     attn_fwd_tail<DMODE, WIDE, Q8>(a, smem, p, h, bi.x * 128);
     return;
   }
-#endif
   const int nkt = (T + 63) >> 6;
   const int qw = bi.x * 128 + wave * 32;
   const bool active = qw < a.Tq;
@@ -980,12 +969,7 @@ __global__ __launch_bounds__(256, DMODE == 0 ? 4 : (WIDE ? 3 : MMSEQ_ATTN_FWD_WP
   const uint32_t boff0 = (uint32_t)(((qw + i) * a.nkt2 * 4 + g) * 2);
   auto stage = [&](int t) {
     unsigned short* kimg = smem + (t & 1) * 2 * IMG;
-    uint32_t lo = loff;
-    if (DMODE == 0 && MMSEQ_ATTN_FWD_RECOMP) {  // recomputed per call (volatile lane copy)
-      uint32_t ln = (uint32_t)lane;
-      asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(ln));
-      lo = dma_lane_off((int)ln, ld);
-    }
+    uint32_t lo = loff;  // a copy by value: reading the capture in the loop compiles to other scalar code
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       const int pc = wave * 2 + e;
@@ -1053,15 +1037,10 @@ __global__ __launch_bounds__(256, DMODE == 0 ? 4 : (WIDE ? 3 : MMSEQ_ATTN_FWD_WP
     constexpr bool FULL = decltype(fullc)::value;
     const unsigned short* kimg = smem + (t & 1) * 2 * IMG;
     const unsigned short* vimg = kimg + IMG;
-    int ro0, ro1, to[4];
-    {
-      uint32_t ln = (uint32_t)lane;
-      if (DMODE == 0 && MMSEQ_ATTN_FWD_RECOMP) asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(ln));
-      ro0 = row_off((int)ln, 0);
-      ro1 = row_off((int)ln, 1);
+    const int ro0 = row_off(lane, 0), ro1 = row_off(lane, 1);
+    int to[4];
 #pragma unroll
-      for (int d = 0; d < 4; ++d) to[d] = tr_off((int)ln, d);
-    }
+    for (int d = 0; d < 4; ++d) to[d] = tr_off(lane, d);
     // 16-key blocks holding a valid key (the last tile of T = 64n + 1 has one): the others are
     // all masked (p = 0), so their MFMAs and softmax work are skipped
     const int nkb = FULL ? 4 : min(4, (T - t * 64 + 15) >> 4);
@@ -1070,12 +1049,13 @@ __global__ __launch_bounds__(256, DMODE == 0 ? 4 : (WIDE ? 3 : MMSEQ_ATTN_FWD_WP
     const bool zb = __builtin_amdgcn_readfirstlane(sZero[t]) != 0;
     bf16x8_t pf[2][2];
     // The first tile runs the max path. Later tiles first take the exponentials against the
-    // running max as it stands and keep them when no row's sum over the tile exceeds 2^8: then no
-    // score is more than 8 (log2 units) above m, the case in which the max path leaves m unchanged
-    // and computes these same exponentials. Otherwise the wave runs the tile again by the max
-    // path (redo), its scores recomputed from the K tile still in LDS (holding them across the
-    // attempt would spill). Saves the per-tile row max (16 max, a scale and a vote per 16-row
-    // group).
+    // running max as it stands and keep them when no row's sum over the tile, rounded to bf16,
+    // exceeds 2^8: that bounds every P of the tile at 2^8 (up to that rounding), which the
+    // accumulators take without rescaling, so the result matches the max path's up to rounding
+    // (not bit for bit: the max path may move m where this keeps it). Otherwise the wave runs the
+    // tile again by the max path (redo), its scores recomputed from the K tile still in LDS
+    // (holding them across the attempt would spill). Saves the per-tile row max (16 max, a scale
+    // and a vote per 16-row group).
     {
       f32x4 s[2][4];
 #pragma unroll
@@ -1223,7 +1203,7 @@ __global__ __launch_bounds__(256, DMODE == 0 ? 4 : (WIDE ? 3 : MMSEQ_ATTN_FWD_WP
       // tile t landed everywhere; buffer (t + 1) & 1 no longer read
       stage(t + 1);
     }
-    if (active && !tile(t, std::true_type{}, !MMSEQ_ATTN_FAST_EXP || t == 0 || redo)) {
+    if (active && !tile(t, std::true_type{}, t == 0 || redo)) {
       redo = true;
       continue;
     }
@@ -1822,14 +1802,9 @@ __device__ __forceinline__ void zero_dq(const AttnArgs& a, unsigned short* row, 
 // Plain blocks of the keep-bit / no-dropout modes: three workgroups per CU (<= 168 VGPRs); in the
 // keep-bit one the lane-derived LDS offsets are recomputed in every tile (volatile lane copy) rather
 // than held across the loop, which at 168 registers spilled them into reloads whose vmcnt wait also
-// drained the next tile's DMA. MMSEQ_DKDV_WG2: the two-workgroup bound for every instantiation (A/B).
-#ifdef MMSEQ_DKDV_WG2
-#define DKDV_WG(FOLD, D) 2
-#else
-#define DKDV_WG(FOLD, D) ((FOLD) || (D) == 1 ? 2 : 3)
-#endif
+// drained the next tile's DMA.
 template <int DMODE, bool FOLD>  // dropout: 0 none, 1 counter hash, 2 keep bits from the forward
-__global__ __launch_bounds__(256, DKDV_WG(FOLD, DMODE)) void attn_dkdv_bf16_kernel(AttnArgs a) {
+__global__ __launch_bounds__(256, FOLD || DMODE == 1 ? 2 : 3) void attn_dkdv_bf16_kernel(AttnArgs a) {
   constexpr bool DROP = DMODE != 0;
   extern __shared__ __attribute__((aligned(16))) unsigned short smem[];  // 2 x (Q, dO) + lse, D
   const int T = a.T, Tq = a.Tq;
@@ -1885,7 +1860,8 @@ __global__ __launch_bounds__(256, DKDV_WG(FOLD, DMODE)) void attn_dkdv_bf16_kern
   const int64_t rb = ((int64_t)p * a.heads + h) * T;
   const rsrc_t rlse = make_rsrc(a.lse + rb, (int64_t)T * 4), rdel = make_rsrc(a.delta + rb, (int64_t)T * 4);
   float lv[4], dlv[4];
-  // sL: L (log2 units), or without dropout -L / c (the S MFMAs' accumulator input, below)
+  // sL: L (log2 units) for DMODE 1; for DMODE 0 and 2 (no dropout, keep bits read) -L / c (the S
+  // MFMAs' accumulator input, below)
   constexpr bool LINIT = DMODE != 1;  // -L/c as the S MFMAs' input
   const float nic = LINIT ? -1.f / (a.scale * LOG2E) : 1.f;
 #pragma unroll
@@ -2018,7 +1994,7 @@ __global__ __launch_bounds__(256, DKDV_WG(FOLD, DMODE)) void attn_dkdv_bf16_kern
     // P / dS, then dV^T[d][key] += dO^T[d][q] P[q][key] and dK^T[d][key] += Q^T[d][q] dS[q][key]
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      // without dropout the row term of P enters as the S MFMAs' accumulator input: S starts at
+      // DMODE 0 and 2 (LINIT): the row term of P enters as the S MFMAs' accumulator input: S starts at
       // -L/c (sL holds it), so S c = Q K^T c - L (sD holds -D; as dP's accumulator input, and in
       // the keep-bit kernel as S's, it spilled)
       // (each accumulator's input read from LDS on its own: a shared register copy would be copied)
@@ -2189,14 +2165,10 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // Row blocks of the tail-folding kernels: T = 128 n + r with 1 <= r <= 16 (T = 513, 393, 769 on the
 // path) runs n blocks, the last one also owning the r tail rows, instead of n + 1 blocks whose last
 // has one active wave; a block's time is set by its key sweep, not by how many of its rows are valid
-// (DESIGN §7), so the n + 1-th block cost a full block. MMSEQ_ATTN_NO_FOLD=1 at build time: off.
+// (DESIGN §7), so the n + 1-th block cost a full block.
 void tail_fold(AttnArgs& a, int T) {  // T = 0: no fold (a.nxq from a.T)
   const int n = T / 128, r = T % 128;
-#ifndef MMSEQ_ATTN_NO_FOLD
   const bool fold = n >= 1 && r >= 1 && r <= 16;
-#else
-  const bool fold = false;
-#endif
   a.tail0 = fold ? n * 128 : 0;
   a.nxq = fold ? n : (a.T + 127) / 128;
 }
@@ -2253,10 +2225,7 @@ static mmseq_status attn_fwd_impl(int P, int T, int Tq, int heads, const void* q
   } else if (dtype == MMSEQ_BF16 && variant) {
     MMSEQ_REQUIRE(aligned16(out) && ld_out % 8 == 0, "attn_fwd: out must be 16-byte aligned rows");
     const dim3 gq((unsigned)(((Tq + 127) / 128) * heads * P));
-    size_t lds = (size_t)4 * 4096 * 2 + (size_t)((T + 63) / 64) * (64 + 1) * 4;
-#ifdef MMSEQ_ATTN_FWD_LDS_PAD  // occupancy experiments: pad the workgroup's LDS
-    lds += MMSEQ_ATTN_FWD_LDS_PAD;
-#endif
+    const size_t lds = (size_t)4 * 4096 * 2 + (size_t)((T + 63) / 64) * (64 + 1) * 4;
     a.bits = keep_bits;
     a.nkt2 = (((T + 63) / 64) + 1) & ~1;
     // largest dropout pair index + the in-tile key offset must stay below 2^32 for the narrow path
@@ -2352,14 +2321,8 @@ static mmseq_status attn_bwd_impl(int P, int T, int Tq, int heads, const void* q
     ak.xoff = 0; ak.nxl = nplain;
     akt.xoff = nplain; akt.nxl = 1;
     const dim3 gdk((unsigned)(nplain * heads * P)), gdt((unsigned)(heads * P));
-#ifdef MMSEQ_ATTN_ONE_DKDV  // A/B: every block in the FOLD kernel (one launch)
-    ak.nxl = ak.nxq; const int ntail = 0;
-    const dim3 gdk1((unsigned)(ak.nxq * heads * P));
-#define DKDV_PLAIN(D) hipLaunchKernelGGL((attn_dkdv_bf16_kernel<D, true>), gdk1, dim3(256), ldsk, s, ak)
-#else
     const int ntail = ak.tail0 ? 1 : 0;
 #define DKDV_PLAIN(D) if (nplain) hipLaunchKernelGGL((attn_dkdv_bf16_kernel<D, false>), gdk, dim3(256), lds, s, ak)
-#endif
 #define DKDV_TAIL(D) if (ntail) hipLaunchKernelGGL((attn_dkdv_bf16_kernel<D, true>), gdt, dim3(256), ldsk, s, akt)
     if (dmode == 2) {
       hipLaunchKernelGGL(attn_dq_bf16_kernel<2>, gdq, dim3(256), ldsq, s, a);

@@ -306,6 +306,24 @@ __global__ __launch_bounds__(256) void quant_mxfp8_kernel(int M, int K, const TI
   *reinterpret_cast<i32x4*>(qp + 16) = (i32x4){(int)w[4], (int)w[5], (int)w[6], (int)w[7]};
 }
 
+// The argument block of an MX-fp8 entry point: C = act(alpha * A B^T + bias), one unsplit K range,
+// no dropout; the entry points add what only they have (residual, aux, q8 / f8 scales).
+GemmArgs mx_args(int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
+                 int64_t ldc, const float* bias, int act, float alpha) {
+  GemmArgs g{};
+  g.M = M; g.N = N; g.K = K;
+  g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
+  g.bias = bias; g.act = act; g.alpha = alpha;
+  g.splitk = 1; g.kchunk = K; g.drop = make_drop(nullptr);
+  return g;
+}
+
+// ... with e4m3 operands: their packed E8M0 scales (the F8 schedule of gemm256.hip)
+void set_f8_scales(GemmArgs& g, const void* a_scales, const void* b_scales) {
+  g.f8_sa = (const uint8_t*)a_scales; g.f8_sb = (const uint8_t*)b_scales;
+  g.f8_sa_bytes = mmseq_mxfp8_scale_bytes(g.M, g.K); g.f8_sb_bytes = mmseq_mxfp8_scale_bytes(g.N, g.K);
+}
+
 }  // namespace
 
 extern "C" int64_t mmseq_mxfp8_scale_bytes(int M, int K) {
@@ -347,15 +365,11 @@ extern "C" mmseq_status mmseq_gemm_mxfp8(int M, int N, int K, const void* A, int
   MMSEQ_REQUIRE(((uintptr_t)C & 7) == 0 && (!resid || ((uintptr_t)resid & 7) == 0),
                 "gemm_mxfp8: 8-byte aligned output");
   if (M == 0) return MMSEQ_OK;
-#ifndef MMSEQ_F8_OLD
+  GemmArgs a = mx_args(M, N, K, A, lda, B, ldb, C, ldc, bias, act, alpha);
+  a.resid = resid; a.ldr = ldr;
   {  // the 256 x 256 8-phase schedule (gemm256.hip, F8) when K % 256 == 0 and there are tiles for it
-    GemmArgs g{};
-    g.M = M; g.N = N; g.K = K;
-    g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
-    g.bias = bias; g.act = act; g.resid = resid; g.ldr = ldr; g.alpha = alpha;
-    g.splitk = 1; g.kchunk = K; g.drop = make_drop(nullptr);
-    g.f8_sa = (const uint8_t*)a_scales; g.f8_sb = (const uint8_t*)b_scales;
-    g.f8_sa_bytes = mmseq_mxfp8_scale_bytes(M, K); g.f8_sb_bytes = mmseq_mxfp8_scale_bytes(N, K);
+    GemmArgs g = a;
+    set_f8_scales(g, a_scales, b_scales);
     hipError_t e = hipSuccess;
     if (M >= 256 && N >= 256 &&
         mmseq_gemm256_nt_f8(g, mmseq_device_cus(), reinterpret_cast<hipStream_t>(stream), &e)) {
@@ -363,16 +377,11 @@ extern "C" mmseq_status mmseq_gemm_mxfp8(int M, int N, int K, const void* A, int
       return mmseq_check_launch("gemm_mxfp8");
     }
   }
-#endif
   // 256 x 256 tiles once there are rows and columns for them, else 128 x 128
   const bool wide = M >= 512 && N >= 256;
   const int tile = wide ? 256 : 128;
   const int tiles_m = (M + tile - 1) / tile, tiles_n = (N + tile - 1) / tile;
   MMSEQ_REQUIRE((int64_t)tiles_m * tiles_n < (1ll << 31), "gemm_mxfp8: too many tiles");
-  GemmArgs a{};
-  a.M = M; a.N = N; a.K = K;
-  a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc;
-  a.bias = bias; a.act = act; a.resid = resid; a.ldr = ldr; a.alpha = alpha;
   a.vec_c = 1;
   hipLaunchKernelGGL(wide ? gemm_mxfp8_nt256x256_kernel : gemm_mxfp8_nt_kernel,
                      dim3(tiles_m * tiles_n), dim3(wide ? 512 : 256), 0,
@@ -407,21 +416,14 @@ extern "C" mmseq_status mmseq_gemm_mxfp8_ex(int M, int N, int K, const void* A, 
   if (M == 0) return MMSEQ_OK;
   if (K % 256 != 0 || M < 256 || N < 256)
     return mmseq_set_error(MMSEQ_EUNSUPPORTED, "gemm_mxfp8_ex: needs K %% 256 == 0 and M, N >= 256");
-  GemmArgs g{};
-  g.M = M; g.N = N; g.K = K;
-  g.A = A; g.lda = lda; g.B = B; g.ldb = ldb;
-  g.bias = bias; g.act = act; g.aux = aux; g.dact = dact; g.resid = resid; g.ldr = resid ? ldr : 0;
-  g.alpha = 1.f; g.splitk = 1; g.kchunk = K;
+  GemmArgs g = mx_args(M, N, K, A, lda, B, ldb, q ? q : C, q ? ldq : ldc, bias, act, 1.f);
+  g.aux = aux; g.dact = dact; g.resid = resid; g.ldr = resid ? ldr : 0;
   g.drop = make_drop(drop);
-  if (q) {
-    g.C = q; g.ldc = ldq;
+  if (q) {  // C is then the bf16 copy
     g.q8_scales = reinterpret_cast<uint8_t*>(q_scales);
     g.cbf = C; g.ldcb = ldc;
-  } else {
-    g.C = C; g.ldc = ldc;
   }
-  g.f8_sa = (const uint8_t*)a_scales; g.f8_sb = (const uint8_t*)b_scales;
-  g.f8_sa_bytes = mmseq_mxfp8_scale_bytes(M, K); g.f8_sb_bytes = mmseq_mxfp8_scale_bytes(N, K);
+  set_f8_scales(g, a_scales, b_scales);
   hipError_t e = hipSuccess;
   MMSEQ_REQUIRE(mmseq_gemm256_nt_f8(g, mmseq_device_cus(), reinterpret_cast<hipStream_t>(stream), &e),
                 "gemm_mxfp8_ex: preconditions (leading dimensions, alignment, epilogue combination)");
@@ -443,11 +445,7 @@ extern "C" mmseq_status mmseq_gemm_mxfp8_out(int M, int N, int K, const void* A,
   MMSEQ_REQUIRE(act == 0 || act == MMSEQ_ACT_GELU_ERF || act == MMSEQ_ACT_QUICKGELU,
                 "gemm_mxfp8_out: act");
   if (M == 0) return MMSEQ_OK;
-  GemmArgs a{};
-  a.M = M; a.N = N; a.K = K;
-  a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = q; a.ldc = ldq;
-  a.bias = bias; a.act = act; a.alpha = 1.f; a.splitk = 1; a.kchunk = K;
-  a.drop = make_drop(nullptr);
+  GemmArgs a = mx_args(M, N, K, A, lda, B, ldb, q, ldq, bias, act, 1.f);
   a.q8_scales = reinterpret_cast<uint8_t*>(scales);
   hipError_t e = hipSuccess;
   MMSEQ_REQUIRE(mmseq_gemm256_nt_q8(a, mmseq_device_cus(), reinterpret_cast<hipStream_t>(stream), &e),
@@ -471,14 +469,9 @@ extern "C" mmseq_status mmseq_gemm_mxfp8_q8(int M, int N, int K, const void* A, 
   MMSEQ_REQUIRE(act == 0 || act == MMSEQ_ACT_GELU_ERF || act == MMSEQ_ACT_QUICKGELU,
                 "gemm_mxfp8_q8: act");
   if (M == 0) return MMSEQ_OK;
-  GemmArgs g{};
-  g.M = M; g.N = N; g.K = K;
-  g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = q; g.ldc = ldq;
-  g.bias = bias; g.act = act; g.alpha = 1.f; g.splitk = 1; g.kchunk = K;
-  g.drop = make_drop(nullptr);
+  GemmArgs g = mx_args(M, N, K, A, lda, B, ldb, q, ldq, bias, act, 1.f);
   g.q8_scales = reinterpret_cast<uint8_t*>(q_scales);
-  g.f8_sa = (const uint8_t*)a_scales; g.f8_sb = (const uint8_t*)b_scales;
-  g.f8_sa_bytes = mmseq_mxfp8_scale_bytes(M, K); g.f8_sb_bytes = mmseq_mxfp8_scale_bytes(N, K);
+  set_f8_scales(g, a_scales, b_scales);
   hipError_t e = hipSuccess;
   MMSEQ_REQUIRE(mmseq_gemm256_nt_f8(g, mmseq_device_cus(), reinterpret_cast<hipStream_t>(stream), &e),
                 "gemm_mxfp8_q8: preconditions");

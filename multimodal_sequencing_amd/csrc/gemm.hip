@@ -17,6 +17,7 @@
 // previous tile) -> LDS after the barrier (the async-STAGE split of the guide, T14).
 #include <cstdlib>
 #include "gemm_common.h"
+#include "gemm_plan.h"
 
 #include <atomic>
 
@@ -724,6 +725,43 @@ hipError_t launch_fast(int trans, const GemmArgs& a, int batch, hipStream_t s, c
 
 inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
+// grid of the split-K reductions: one thread per 4 outputs, grid-stride beyond 4096 blocks
+inline unsigned reduce_blocks(int64_t items) {
+  return (unsigned)((items + 255) / 256 < 4096 ? (items + 255) / 256 : 4096);
+}
+
+// The 256 x 256 TN weight-gradient path on prepared arguments: plan the K split for this workspace,
+// launch the kernel, then the reduction the plan needs: the slab and the bias partial rows in one
+// launch (wgrad_reduce_kernel), the slab alone (splitk_reduce_kernel), or none. Returns false
+// with nothing launched when the kernel's preconditions fail (the caller takes its next path).
+bool wgrad_tn256(GemmArgs t, float* bias_grad, float* ws, int64_t ws_bytes, int num_cu,
+                 hipStream_t s, const char* what, mmseq_status* st) {
+  const int M = t.M, N = t.N, tn256 = (N + 255) / 256;
+  const mmseq_gemm_plan::SplitPlan p =
+      mmseq_gemm_plan::plan_tn256(M, N, t.K, num_cu, ws_bytes, bias_grad != nullptr);
+  t.splitk = p.splitk; t.kchunk = p.kchunk; t.slab = ws;
+  // the bias gradient's partials [split][column tile][M] (balanced over the column tiles, summed
+  // in fixed order by wgrad_reduce_kernel); without workspace room the first column tile adds
+  // them directly
+  t.cs = bias_grad;
+  t.cs_slab = p.cs_off >= 0 ? ws + p.cs_off : nullptr;
+  hipError_t e = hipSuccess;
+  if (!mmseq_gemm256_tn(t, s, &e)) return false;
+  float* const C = reinterpret_cast<float*>(t.C);
+  const unsigned blocks = t.splitk > 1 ? reduce_blocks((int64_t)M * N / 4) : 0;
+  if (e == hipSuccess && t.cs_slab) {
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks + (M + 31) / 32), dim3(256), 0, s, M, N,
+                       t.splitk, ws, C, t.ldc, (int)blocks, t.splitk * tn256, t.cs_slab, bias_grad);
+    e = hipGetLastError();
+  } else if (e == hipSuccess && blocks) {
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, M, N, t.splitk, ws, C,
+                       t.ldc, t.accumulate);
+    e = hipGetLastError();
+  }
+  *st = e == hipSuccess ? MMSEQ_OK : mmseq_set_error(MMSEQ_EHIP, "%s: %s", what, hipGetErrorString(e));
+  return true;
+}
+
 }  // namespace
 
 extern "C" mmseq_status mmseq_gemm(int trans, int M, int N, int K, int batch, const void* A,
@@ -754,7 +792,6 @@ extern "C" mmseq_status mmseq_gemm(int trans, int M, int N, int K, int batch, co
   if (M == 0 || N == 0) return MMSEQ_OK;
   float* const g_slab = reinterpret_cast<float*>(workspace);
   const int64_t g_slab_bytes = workspace ? workspace_bytes : 0;
-  const int g_num_cu = sel.num_cu;
   GemmArgs a{};
   a.M = M; a.N = N; a.K = K;
   a.A = A; a.lda = lda; a.sA = strideA;
@@ -778,54 +815,22 @@ extern "C" mmseq_status mmseq_gemm(int trans, int M, int N, int K, int batch, co
   a.splitk = 1; a.kchunk = K; a.slab = nullptr;
   a.cs = nullptr; a.cs_slab = nullptr;
   if (fast_ok) {
-    const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
     const bool plain = !bias && !act && !aux_out && !dact_aux && !resid && alpha == 1.0f &&
                        !a.drop.thr &&
                        out_dtype == MMSEQ_F32 && batch == 1 && ldc % 4 == 0 && al16(C);
     // weight gradients: 256 x 256 TN kernel, K split so that (tiles x splits) fills the CUs
-    if (trans && plain && sel.big) {
-      const int t256 = ((M + 255) / 256) * ((N + 255) / 256);
-      int S2 = t256 < g_num_cu ? g_num_cu / t256 : 1;
-      if (S2 > K / 1024) S2 = K / 1024 > 0 ? K / 1024 : 1;
-      while (S2 > 1 && (!g_slab || (int64_t)S2 * M * N * 4 > g_slab_bytes)) --S2;
-      GemmArgs t = a;
-      t.splitk = S2;
-      t.kchunk = ((K + S2 - 1) / S2 + 127) / 128 * 128;
-      t.splitk = (K + t.kchunk - 1) / t.kchunk;
-      t.slab = g_slab;
-      hipError_t e2 = hipSuccess;
-      if (t.splitk <= 1) { t.splitk = 1; t.kchunk = K; }
-      if (mmseq_gemm256_tn(t, s, &e2)) {
-        if (e2 == hipSuccess && t.splitk > 1) {
-          int64_t t4 = (int64_t)M * N / 4;
-          unsigned blocks = (unsigned)((t4 + 255) / 256 < 4096 ? (t4 + 255) / 256 : 4096);
-          hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, M, N, t.splitk,
-                             g_slab, (float*)C, ldc, accumulate);
-          e2 = hipGetLastError();
-        }
-        if (e2 != hipSuccess) return mmseq_set_error(MMSEQ_EHIP, "gemm launch: %s", hipGetErrorString(e2));
-        return MMSEQ_OK;
-      }
-    }
-    int S = 1;
-    if (trans && plain && g_slab && tiles < 512) {
-      S = (1024 + tiles - 1) / tiles;
-      const int maxS = K / (64 * 16);  // keep >= 16 K-steps per split
-      if (S > maxS) S = maxS;
-      while (S > 1 && (int64_t)S * M * N * 4 > g_slab_bytes) --S;
-    }
-    if (S > 1) {
-      a.splitk = S;
-      a.kchunk = ((K + S - 1) / S + 63) / 64 * 64;
-      S = (K + a.kchunk - 1) / a.kchunk;
-      a.splitk = S;
-      a.slab = g_slab;
+    mmseq_status st;
+    if (trans && plain && sel.big &&
+        wgrad_tn256(a, nullptr, g_slab, g_slab_bytes, sel.num_cu, s, "gemm launch", &st))
+      return st;
+    mmseq_gemm_plan::SplitPlan p{1, K, 0, -1, 0};
+    if (trans && plain && g_slab) p = mmseq_gemm_plan::plan_tn128(M, N, K, g_slab_bytes);
+    if (p.splitk > 1) {
+      a.splitk = p.splitk; a.kchunk = p.kchunk; a.slab = g_slab;
       e = launch_fast<float>(trans, a, 1, s, sel);
       if (e == hipSuccess) {
-        int64_t t4 = (int64_t)M * N / 4;
-        unsigned blocks = (unsigned)((t4 + 255) / 256 < 4096 ? (t4 + 255) / 256 : 4096);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, M, N, S, g_slab,
-                           (float*)C, ldc, accumulate);
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(reduce_blocks((int64_t)M * N / 4)), dim3(256),
+                           0, s, M, N, p.splitk, g_slab, (float*)C, ldc, accumulate);
         e = hipGetLastError();
       }
     } else {
@@ -837,15 +842,9 @@ extern "C" mmseq_status mmseq_gemm(int trans, int M, int N, int K, int batch, co
     // fp32 GEMMs with few output tiles (the BERSON head: M = 16-400 rows per story batch, and
     // its weight gradients over all tokens): split K over the CUs, fp32 partial slabs, a
     // fixed-order reduction that applies the epilogue (bitwise reproducible)
-    const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
-    int S = (g_num_cu + tiles - 1) / tiles;
-    if (S > K / 128) S = K / 128;
-    while (S > 1 && (int64_t)S * M * N * 4 > g_slab_bytes) --S;
-    a.splitk = S;
-    a.kchunk = ((K + S - 1) / S + 31) / 32 * 32;
-    a.splitk = (K + a.kchunk - 1) / a.kchunk;
-    a.slab = g_slab;
-    if (a.splitk > 1) {
+    const mmseq_gemm_plan::SplitPlan p = mmseq_gemm_plan::plan_f32(M, N, K, sel.num_cu, g_slab_bytes);
+    if (p.splitk > 1) {
+      a.splitk = p.splitk; a.kchunk = p.kchunk; a.slab = g_slab;
       dim3 grid((N + BN - 1) / BN, (M + BM - 1) / BM, a.splitk);
       if (trans)
         hipLaunchKernelGGL((gemm_kernel<float, float, true>), grid, dim3(NT_THREADS), 0, s, a);
@@ -853,13 +852,11 @@ extern "C" mmseq_status mmseq_gemm(int trans, int M, int N, int K, int batch, co
         hipLaunchKernelGGL((gemm_kernel<float, float, false>), grid, dim3(NT_THREADS), 0, s, a);
       e = hipGetLastError();
       if (e == hipSuccess) {
-        const int64_t tot = (int64_t)M * ((N + 3) / 4);
-        const unsigned blocks = (unsigned)((tot + 255) / 256 < 4096 ? (tot + 255) / 256 : 4096);
-        hipLaunchKernelGGL(splitk_epi_kernel, dim3(blocks), dim3(256), 0, s, a, a.splitk, g_slab);
+        hipLaunchKernelGGL(splitk_epi_kernel, dim3(reduce_blocks((int64_t)M * ((N + 3) / 4))),
+                           dim3(256), 0, s, a, a.splitk, g_slab);
         e = hipGetLastError();
       }
     } else {
-      a.splitk = 1; a.kchunk = K; a.slab = nullptr;
       e = launch<float, float>(trans, a, batch, s);
     }
   } else if (in_dtype == MMSEQ_BF16 && out_dtype == MMSEQ_BF16)
@@ -874,28 +871,12 @@ extern "C" mmseq_status mmseq_gemm(int trans, int M, int N, int K, int batch, co
   return MMSEQ_OK;
 }
 
-// Upper bound of the split-K slab bytes any path of mmseq_gemm / mmseq_gemm_wgrad picks for this
-// shape on the current device (less workspace only lowers the split count).
+// Workspace bytes beyond which no path of mmseq_gemm / mmseq_gemm_wgrad changes its plan for this
+// shape on the current device: the largest of what the three split-K plans use unlimited, bias
+// partial rows included (less workspace lowers the split count or drops the partial rows).
 extern "C" int64_t mmseq_gemm_workspace_size(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const int64_t cus = device_cus(), MN = (int64_t)M * N;
-  int64_t best = 0;
-  const int64_t t256 = (int64_t)((M + 255) / 256) * ((N + 255) / 256);
-  int64_t s2 = t256 < cus ? cus / t256 : 1;
-  if (s2 > K / 1024) s2 = K / 1024 > 0 ? K / 1024 : 1;
-  if (s2 > 1) best = s2 * ((int64_t)((N + 255) / 256) * M + MN) * 4;  // + bias partials per column tile
-  const int64_t tiles = (int64_t)((M + 127) / 128) * ((N + 127) / 128);
-  if (tiles < 512) {
-    int64_t s = (1024 + tiles - 1) / tiles;
-    if (s > K / 1024) s = K / 1024;
-    if (s > 1 && s * MN * 4 > best) best = s * MN * 4;
-  }
-  if (tiles < 128 && K >= 256) {
-    int64_t s = (cus + tiles - 1) / tiles;
-    if (s > K / 128) s = K / 128;
-    if (s > 1 && s * MN * 4 > best) best = s * MN * 4;
-  }
-  return best;
+  return mmseq_gemm_plan::workspace_bound(M, N, K, device_cus());
 }
 
 // Weight gradient with the fused bias gradient (include/mmseq.h): C[M][N] += A^T B and
@@ -920,7 +901,6 @@ extern "C" mmseq_status mmseq_gemm_wgrad(int M, int N, int K, const void* A, int
   if (M == 0 || N == 0 || K == 0) return MMSEQ_OK;
   float* const g_slab = reinterpret_cast<float*>(workspace);
   const int64_t g_slab_bytes = workspace ? workspace_bytes : 0;
-  const int g_num_cu = sel.num_cu;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   // the split-K reduction does f32x4 read-modify-writes on C: 16-byte aligned rows only
   const bool c_vec = ((uintptr_t)C & 15) == 0 && ldc % 4 == 0;
@@ -932,43 +912,8 @@ extern "C" mmseq_status mmseq_gemm_wgrad(int M, int N, int K, const void* A, int
     t.A = A; t.lda = lda; t.B = B; t.ldb = ldb; t.C = C; t.ldc = ldc;
     t.alpha = 1.f; t.accumulate = 1;
     t.drop = make_drop(nullptr);
-    const int t256 = ((M + 255) / 256) * ((N + 255) / 256);
-    int S2 = t256 < g_num_cu ? g_num_cu / t256 : 1;
-    if (S2 > K / 1024) S2 = K / 1024 > 0 ? K / 1024 : 1;
-    const int tn256 = (N + 255) / 256;
-    const int64_t cs_rows = bias_grad ? (int64_t)tn256 * M : 0;  // one partial row per column tile
-    while (S2 > 1 && (!g_slab || (int64_t)S2 * (cs_rows + (int64_t)M * N) * 4 > g_slab_bytes)) --S2;
-    t.splitk = S2;
-    t.kchunk = ((K + S2 - 1) / S2 + 127) / 128 * 128;
-    t.splitk = (K + t.kchunk - 1) / t.kchunk;
-    if (t.splitk <= 1) { t.splitk = 1; t.kchunk = K; }
-    t.slab = g_slab;
-    t.cs = bias_grad;
-    // the bias gradient's partials [split][column tile][M] (balanced over the column tiles, summed
-    // in fixed order by wgrad_reduce_kernel); without workspace room the first column tile adds
-    // them directly
-    const int64_t slab_c = t.splitk > 1 ? (int64_t)t.splitk * M * N : 0;
-    t.cs_slab = bias_grad && g_slab &&
-                        (slab_c + (int64_t)t.splitk * tn256 * M) * 4 <= g_slab_bytes
-                    ? g_slab + slab_c : nullptr;
-    hipError_t e2 = hipSuccess;
-    if (mmseq_gemm256_tn(t, s, &e2)) {
-      const int64_t t4 = (int64_t)M * N / 4;
-      const unsigned blocks =
-          t.splitk > 1 ? (unsigned)((t4 + 255) / 256 < 4096 ? (t4 + 255) / 256 : 4096) : 0;
-      if (e2 == hipSuccess && t.cs_slab) {  // the slab and the bias partial rows in one launch
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks + (M + 31) / 32), dim3(256), 0, s, M, N,
-                           t.splitk, g_slab, C, ldc, (int)blocks, t.splitk * tn256, t.cs_slab,
-                           bias_grad);
-        e2 = hipGetLastError();
-      } else if (e2 == hipSuccess && blocks) {
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, M, N, t.splitk,
-                           g_slab, C, ldc, 1);
-        e2 = hipGetLastError();
-      }
-      if (e2 != hipSuccess) return mmseq_set_error(MMSEQ_EHIP, "gemm_wgrad: %s", hipGetErrorString(e2));
-      return MMSEQ_OK;
-    }
+    mmseq_status st;
+    if (wgrad_tn256(t, bias_grad, g_slab, g_slab_bytes, sel.num_cu, s, "gemm_wgrad", &st)) return st;
   }
   mmseq_status st = mmseq_gemm(1, M, N, K, 1, A, lda, 0, B, ldb, 0, C, ldc, 0, nullptr, 0, nullptr,
                                nullptr, nullptr, 0, 0, 1.0f, 1, in_dtype, MMSEQ_F32, nullptr,

@@ -103,11 +103,7 @@ __device__ __forceinline__ void epi8(const GemmArgs& a, int m, int n, f32x4 lo, 
   } else {
     bias_alpha8(v, lo, hi, a.alpha, bias.b0, bias.b1);
   }
-#ifdef MMSEQ_EPI_SINK  // experiment: every tile stores into rows 0-255 (L2-resident, no HBM writes)
-  const int64_t off = (int64_t)(m & 255) * a.ldc + n;
-#else
   const int64_t off = (int64_t)m * a.ldc + n;
-#endif
   if (BWD) {
     if (DTAB) {
 #pragma unroll
@@ -262,15 +258,10 @@ constexpr int G_LDA_HALF = 16384;  // elements per 256 x 64 operand image
 // of NT_GROUP_M_AUX at >= 12 N tiles: at N = 3072 (the FC1 forward of a training step) 818-820
 // TF/s with 16 against 783-787 with 8, at N = 2304 16 was slower (772 vs 792), the other
 // epilogues equal either way (profiles/r6_v19_nt_group_m_ab.txt, r6_v20_nt_group_m_aux_ab.txt).
-#ifndef MMSEQ_NT_GROUP_M
-#define MMSEQ_NT_GROUP_M 8
-#endif
-#ifndef MMSEQ_NT_GROUP_M_AUX
-#define MMSEQ_NT_GROUP_M_AUX 16
-#endif
+constexpr int NT_GROUP_M = 8, NT_GROUP_M_AUX = 16;
 __device__ __forceinline__ void tile_mn(int tile, int tiles_n, int ntiles, int& tm, int& tn,
                                         bool aux2 = false) {
-  const int GM = tiles_n >= 8 ? (aux2 && tiles_n >= 12 ? MMSEQ_NT_GROUP_M_AUX : MMSEQ_NT_GROUP_M) : 1;
+  const int GM = tiles_n >= 8 ? (aux2 && tiles_n >= 12 ? NT_GROUP_M_AUX : NT_GROUP_M) : 1;
   if (GM <= 1) {
     tm = tile / tiles_n;
     tn = tile - tm * tiles_n;
@@ -646,12 +637,9 @@ _Pragma("unroll") \
                                         t ? bias1 : bias0, dtab); \
           } \
       }
-#ifndef MMSEQ_EPI_CHECK_ALL
       if (!(Q8 && BWD) && (ACT == 0 || BWD) && m0 + 256 <= a.M && n0 + 256 <= a.N) {
         XIN_EPI(false)
-      } else
-#endif
-      {
+      } else {
         XIN_EPI(true)
       }
 #undef XIN_EPI
@@ -668,8 +656,7 @@ _Pragma("unroll") \
       q8_scale_words(a, m0 + wr * 128 + (g >> 1) * 64 + ii, n0 + wc * 64 + 32 * (g & 1), sq8, lane_e);
     } else {
       const EpiIn none = {(u16x8){0, 0, 0, 0, 0, 0, 0, 0}};
-#ifndef MMSEQ_EPI_CHECK_ALL  // interior tiles without the per-call bounds branches
-      if (m0 + 256 <= a.M && n0 + 256 <= a.N) {
+      if (m0 + 256 <= a.M && n0 + 256 <= a.N) {  // interior tiles without the per-call bounds branches
 #pragma unroll
         for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -677,7 +664,6 @@ _Pragma("unroll") \
             epi8<ACT, BWD, false, false, false>(a, m0 + wr * 128 + i * 16 + ii, n0 + wc * 64 + 32 * t + 8 * g,
                                                 acc[i][2 * t], acc[i][2 * t + 1], none, t ? bias1 : bias0);
       } else
-#endif
 #pragma unroll
       for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -1097,8 +1083,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_2b_kernel(GemmArgs a, int tile
       }
     } else {
       const EpiIn none = {(u16x8){0, 0, 0, 0, 0, 0, 0, 0}};
-#ifndef MMSEQ_EPI_CHECK_ALL  // interior tiles without the per-call bounds branches
-      if (m0 + 256 <= a.M && n0 + 256 <= a.N) {
+      if (m0 + 256 <= a.M && n0 + 256 <= a.N) {  // interior tiles without the per-call bounds branches
 #pragma unroll
         for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -1106,7 +1091,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_2b_kernel(GemmArgs a, int tile
             epi8<ACT, BWD, false, false, false>(a, m0 + wr * 128 + i * 16 + ii, n0 + wc * 64 + 32 * t + 8 * g,
                                                 acc[i][2 * t], acc[i][2 * t + 1], none, t ? bias1 : bias0);
       } else
-#endif
 #pragma unroll
       for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -1399,6 +1383,11 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmArgs a, int tiles_n
 
 }  // namespace
 
+// The host entry points below map (act, bwd, xin, aux, q8) to a kernel instantiation in one form:
+// a one-line launch macro for the kernel at hand, a ladder over the epilogue flags that is the same
+// for both activations (the *_ROW macro), and a switch over the activation (0, GELU, QuickGELU:
+// checked before) whose case 0 spells out its own, shorter ladder. Only the combinations listed
+// are instantiated.
 bool mmseq_gemm256_nt(const GemmArgs& a, bool out_bf16, int num_cu, hipStream_t s, hipError_t* err,
                       int variant, int delay) {
   auto a16 = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
@@ -1411,65 +1400,63 @@ bool mmseq_gemm256_nt(const GemmArgs& a, bool out_bf16, int num_cu, hipStream_t 
   const bool bwd = a.dact != nullptr;
   const bool xin = bwd || a.resid || a.accumulate;
   const bool noepi = a.act == 0 && a.alpha == -12345.0f;  // benchmark hook (tools/gemm_epi_bench.py)
-#define NT_DISPATCH(KERNEL, GRID, BLOCK)                                                            \
-  switch (a.act) {                                                                                  \
-    case 0:                                                                                         \
-      if (noepi) hipLaunchKernelGGL((KERNEL<-1, false, false>), GRID, BLOCK, 0, s, a, tn, ntiles, delay);  \
-      else if (xin) hipLaunchKernelGGL((KERNEL<0, false, true>), GRID, BLOCK, 0, s, a, tn, ntiles, delay); \
-      else hipLaunchKernelGGL((KERNEL<0, false, false>), GRID, BLOCK, 0, s, a, tn, ntiles, delay);         \
-      break;                                                                                        \
-    case MMSEQ_ACT_GELU_ERF:                                                                        \
-      if (bwd) hipLaunchKernelGGL((KERNEL<MMSEQ_ACT_GELU_ERF, true, true>), GRID, BLOCK, 0, s, a, tn, ntiles, delay);        \
-      else if (xin) hipLaunchKernelGGL((KERNEL<MMSEQ_ACT_GELU_ERF, false, true>), GRID, BLOCK, 0, s, a, tn, ntiles, delay); \
-      else hipLaunchKernelGGL((KERNEL<MMSEQ_ACT_GELU_ERF, false, false>), GRID, BLOCK, 0, s, a, tn, ntiles, delay);         \
-      break;                                                                                        \
-    default:                                                                                        \
-      if (bwd) hipLaunchKernelGGL((KERNEL<MMSEQ_ACT_QUICKGELU, true, true>), GRID, BLOCK, 0, s, a, tn, ntiles, delay);        \
-      else if (xin) hipLaunchKernelGGL((KERNEL<MMSEQ_ACT_QUICKGELU, false, true>), GRID, BLOCK, 0, s, a, tn, ntiles, delay); \
-      else hipLaunchKernelGGL((KERNEL<MMSEQ_ACT_QUICKGELU, false, false>), GRID, BLOCK, 0, s, a, tn, ntiles, delay);         \
+#define NT_ROW(L, ACT_)                \
+  if (bwd) L(ACT_, true, true);        \
+  else if (xin) L(ACT_, false, true);  \
+  else L(ACT_, false, false)
+#define NT_LADDER(L)                                       \
+  switch (a.act) {                                         \
+    case 0:                                                \
+      if (noepi) L(-1, false, false);                      \
+      else if (xin) L(0, false, true);                     \
+      else L(0, false, false);                             \
+      break;                                               \
+    case MMSEQ_ACT_GELU_ERF: NT_ROW(L, MMSEQ_ACT_GELU_ERF); break; \
+    default: NT_ROW(L, MMSEQ_ACT_QUICKGELU);               \
   }
   if (variant == 2) {  // ping-pong: two 4-wave groups of 256 x 128 tiles per 512-thread block
     const int tn = (a.N + 127) / 128;
     const int ntiles = ((a.M + 255) / 256) * tn;
     const int grid = (ntiles + 1) / 2 < num_cu ? (ntiles + 1) / 2 : num_cu;
     const bool aux = a.aux != nullptr;
-    const dim3 GR(grid), BL(512);
 #define PP(ACT_, BWD_, XIN_, AUX_) \
-    hipLaunchKernelGGL((gemm_pp_kernel<ACT_, BWD_, XIN_, AUX_>), GR, BL, 0, s, a, tn, ntiles, 0)
+    hipLaunchKernelGGL((gemm_pp_kernel<ACT_, BWD_, XIN_, AUX_>), dim3(grid), dim3(512), 0, s, a, tn, ntiles, 0)
+#define PP_ROW(ACT_)                                   \
+    if (bwd) PP(ACT_, true, true, false);              \
+    else if (xin && aux) PP(ACT_, false, true, true);  \
+    else if (xin) PP(ACT_, false, true, false);        \
+    else if (aux) PP(ACT_, false, false, true);        \
+    else PP(ACT_, false, false, false)
     switch (a.act) {
       case 0:
         if (noepi) PP(-1, false, false, false);
         else if (xin) PP(0, false, true, false);
         else PP(0, false, false, false);
         break;
-      case MMSEQ_ACT_GELU_ERF:
-        if (bwd) PP(MMSEQ_ACT_GELU_ERF, true, true, false);
-        else if (xin) { if (aux) PP(MMSEQ_ACT_GELU_ERF, false, true, true); else PP(MMSEQ_ACT_GELU_ERF, false, true, false); }
-        else if (aux) PP(MMSEQ_ACT_GELU_ERF, false, false, true);
-        else PP(MMSEQ_ACT_GELU_ERF, false, false, false);
-        break;
-      default:
-        if (bwd) PP(MMSEQ_ACT_QUICKGELU, true, true, false);
-        else if (xin) { if (aux) PP(MMSEQ_ACT_QUICKGELU, false, true, true); else PP(MMSEQ_ACT_QUICKGELU, false, true, false); }
-        else if (aux) PP(MMSEQ_ACT_QUICKGELU, false, false, true);
-        else PP(MMSEQ_ACT_QUICKGELU, false, false, false);
+      case MMSEQ_ACT_GELU_ERF: PP_ROW(MMSEQ_ACT_GELU_ERF); break;
+      default: PP_ROW(MMSEQ_ACT_QUICKGELU);
     }
+#undef PP_ROW
 #undef PP
-    *err = hipGetLastError();
-    return true;
-  }
-  if (variant == 1 && a.K % 32 == 0) {  // two 256 x 128 blocks per CU
+  } else if (variant == 1 && a.K % 32 == 0) {  // two 256 x 128 blocks per CU
     const int tn = (a.N + 127) / 128;
     const int ntiles = ((a.M + 255) / 256) * tn;
     const int grid = ntiles < 2 * num_cu ? ntiles : 2 * num_cu;
-    NT_DISPATCH(gemm_nt_2b_kernel, dim3(grid), dim3(256))
+#define NT2B(ACT_, BWD_, XIN_) \
+    hipLaunchKernelGGL((gemm_nt_2b_kernel<ACT_, BWD_, XIN_>), dim3(grid), dim3(256), 0, s, a, tn, ntiles, delay)
+    NT_LADDER(NT2B)
+#undef NT2B
   } else {
     const int tn = (a.N + 255) / 256;
     const int ntiles = ((a.M + 255) / 256) * tn;
     const int grid = ntiles < num_cu ? ntiles : num_cu;
-    NT_DISPATCH(gemm256_nt_kernel, dim3(grid), dim3(512))
+#define NT8(ACT_, BWD_, XIN_) \
+    hipLaunchKernelGGL((gemm256_nt_kernel<ACT_, BWD_, XIN_>), dim3(grid), dim3(512), 0, s, a, tn, ntiles, delay)
+    NT_LADDER(NT8)
+#undef NT8
   }
-#undef NT_DISPATCH
+#undef NT_LADDER
+#undef NT_ROW
   *err = hipGetLastError();
   return true;
 }
@@ -1498,12 +1485,14 @@ bool mmseq_gemm256_nt_q8(const GemmArgs& a, int num_cu, hipStream_t s, hipError_
   const int tn = (a.N + 255) / 256;
   const int ntiles = ((a.M + 255) / 256) * tn;
   const dim3 grid(ntiles < num_cu ? ntiles : num_cu), block(512);
-  if (a.act == MMSEQ_ACT_GELU_ERF)
-    hipLaunchKernelGGL((gemm256_nt_kernel<MMSEQ_ACT_GELU_ERF, false, false, true>), grid, block, 0, s, a, tn, ntiles, 0);
-  else if (a.act == MMSEQ_ACT_QUICKGELU)
-    hipLaunchKernelGGL((gemm256_nt_kernel<MMSEQ_ACT_QUICKGELU, false, false, true>), grid, block, 0, s, a, tn, ntiles, 0);
-  else
-    hipLaunchKernelGGL((gemm256_nt_kernel<0, false, false, true>), grid, block, 0, s, a, tn, ntiles, 0);
+#define NT_Q8(ACT_) \
+  hipLaunchKernelGGL((gemm256_nt_kernel<ACT_, false, false, true>), grid, block, 0, s, a, tn, ntiles, 0)
+  switch (a.act) {
+    case 0: NT_Q8(0); break;
+    case MMSEQ_ACT_GELU_ERF: NT_Q8(MMSEQ_ACT_GELU_ERF); break;
+    default: NT_Q8(MMSEQ_ACT_QUICKGELU);
+  }
+#undef NT_Q8
   *err = hipGetLastError();
   return true;
 }
@@ -1531,31 +1520,25 @@ bool mmseq_gemm256_nt_f8(const GemmArgs& a, int num_cu, hipStream_t s, hipError_
   const int tn = (a.N + 255) / 256;
   const int ntiles = ((a.M + 255) / 256) * tn;
   const dim3 grid(ntiles < num_cu ? ntiles : num_cu), block(512);
-#define F8_LAUNCH(ACT, XIN, Q8) \
-  hipLaunchKernelGGL((gemm256_nt_kernel<ACT, false, XIN, Q8, true>), grid, block, 0, s, a, tn, ntiles, 0)
-  if (a.dact && q8) {
-    if (a.act == MMSEQ_ACT_GELU_ERF)
-      hipLaunchKernelGGL((gemm256_nt_kernel<MMSEQ_ACT_GELU_ERF, true, true, true, true>), grid, block, 0, s, a, tn, ntiles, 0);
-    else
-      hipLaunchKernelGGL((gemm256_nt_kernel<MMSEQ_ACT_QUICKGELU, true, true, true, true>), grid, block, 0, s, a, tn, ntiles, 0);
-  } else if (a.dact) {
-    if (a.act == MMSEQ_ACT_GELU_ERF)
-      hipLaunchKernelGGL((gemm256_nt_kernel<MMSEQ_ACT_GELU_ERF, true, true, false, true>), grid, block, 0, s, a, tn, ntiles, 0);
-    else
-      hipLaunchKernelGGL((gemm256_nt_kernel<MMSEQ_ACT_QUICKGELU, true, true, false, true>), grid, block, 0, s, a, tn, ntiles, 0);
-  } else if (q8) {
-    if (a.act == MMSEQ_ACT_GELU_ERF) F8_LAUNCH(MMSEQ_ACT_GELU_ERF, false, true);
-    else if (a.act == MMSEQ_ACT_QUICKGELU) F8_LAUNCH(MMSEQ_ACT_QUICKGELU, false, true);
-    else F8_LAUNCH(0, false, true);
-  } else if (a.resid) {
-    if (a.act == MMSEQ_ACT_GELU_ERF) F8_LAUNCH(MMSEQ_ACT_GELU_ERF, true, false);
-    else if (a.act == MMSEQ_ACT_QUICKGELU) F8_LAUNCH(MMSEQ_ACT_QUICKGELU, true, false);
-    else F8_LAUNCH(0, true, false);
-  } else {
-    if (a.act == MMSEQ_ACT_GELU_ERF) F8_LAUNCH(MMSEQ_ACT_GELU_ERF, false, false);
-    else if (a.act == MMSEQ_ACT_QUICKGELU) F8_LAUNCH(MMSEQ_ACT_QUICKGELU, false, false);
-    else F8_LAUNCH(0, false, false);
+#define F8_LAUNCH(ACT_, BWD_, XIN_, Q8_) \
+  hipLaunchKernelGGL((gemm256_nt_kernel<ACT_, BWD_, XIN_, Q8_, true>), grid, block, 0, s, a, tn, ntiles, 0)
+  const bool bwd = a.dact != nullptr, xin = a.resid != nullptr;  // bwd: act != 0 (checked above)
+#define F8_ROW(ACT_)                                      \
+  if (bwd && q8) F8_LAUNCH(ACT_, true, true, true);       \
+  else if (bwd) F8_LAUNCH(ACT_, true, true, false);       \
+  else if (q8) F8_LAUNCH(ACT_, false, false, true);       \
+  else if (xin) F8_LAUNCH(ACT_, false, true, false);      \
+  else F8_LAUNCH(ACT_, false, false, false)
+  switch (a.act) {
+    case 0:
+      if (q8) F8_LAUNCH(0, false, false, true);
+      else if (xin) F8_LAUNCH(0, false, true, false);
+      else F8_LAUNCH(0, false, false, false);
+      break;
+    case MMSEQ_ACT_GELU_ERF: F8_ROW(MMSEQ_ACT_GELU_ERF); break;
+    default: F8_ROW(MMSEQ_ACT_QUICKGELU);
   }
+#undef F8_ROW
 #undef F8_LAUNCH
   *err = hipGetLastError();
   return true;

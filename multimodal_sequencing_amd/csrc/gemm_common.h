@@ -133,5 +133,6 @@ bool mmseq_gemm256_nt_f8(const mmseq_gemm_detail::GemmArgs& a, int num_cu, hipSt
 // CU count of the current device (write-once per-device table, gemm.hip)
 int mmseq_device_cus();
 // 256 x 256 TN (wgrad) kernel, fp32 out: a.splitk / a.kchunk (multiple of 128) / a.slab set by the
-// caller (slab [splitk][M][N] when splitk > 1); returns false when its preconditions fail
+// caller from gemm_plan.h's plan_tn256 (slab [splitk][M][N] when splitk > 1); returns false when
+// its preconditions fail
 bool mmseq_gemm256_tn(const mmseq_gemm_detail::GemmArgs& a, hipStream_t s, hipError_t* err);

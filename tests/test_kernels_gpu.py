@@ -103,7 +103,7 @@ def test_gemm_fast_strided_batched():
 
 @pytest.mark.parametrize("fast", [1, 4])
 def test_gemm_big_tile_path(fast):
-    # >= 512 256x256 tiles selects the 256^2 NT kernel by default; ragged M edge, GELU + aux +
+    # >= 256 256x256 tiles (here 130 x 4) selects the 256^2 NT kernel by default; ragged M edge, GELU + aux +
     # residual epilogue; mode 4 also runs it batched with strides
     nat.gemm_set_fast(fast)
     M, Nn, K = 33000 + 77, 1024, 256

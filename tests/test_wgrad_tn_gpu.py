@@ -10,7 +10,10 @@ K: 128 and 256 (one and two 128-row steps, unsplit: the kernel accumulates into 
 of 14, so every split gives every one of three column tiles at least four K-tiles).
 
 Each case runs with the bias gradient, without it, and with no workspace (then the K range is not
-split and the first column tile's blocks add the column sums to db directly). Reference: float64
+split and the first column tile's blocks add the column sums to db directly). The smallest shapes
+that split (256 x 256 and 264 x 520 at K = 4100, 264 x 520 at K = 12416) also run with a
+workspace of exactly two splits and their bias partial rows, 2 (tn256 M + M N) floats: the planner
+then stops in the middle of its fit loop (two splits instead of four or twelve). Reference: float64
 dY^T X and column sums of the same bf16 inputs; bound 1e-4 sqrt(K) (1 + max |ref|), as
 test_gemm_wgrad_fused_bias. Two consecutive calls must agree bit for bit.
 """
@@ -30,13 +33,22 @@ CASES = [(M, N, K) for (M, N) in ((256, 256), (264, 520), (768, 256), (256, 768)
 CASES.append((2304, 768, 4100))
 
 
+TWO_SPLITS = "two splits"
+TWO_SPLIT_CASES = ((256, 256, 4100), (264, 520, 4100), (264, 520, 12416))
+
+
 def _wgrad(dY, X, gW, gb, workspace):
-    """mmseq_gemm_wgrad with the binding's workspace or with none at all."""
+    """mmseq_gemm_wgrad with the binding's workspace, with none at all, or (TWO_SPLITS) with the
+    binding's buffer and workspace_bytes for two splits with their bias partial rows."""
     ws = nat.gemm_workspace(dY.device) if workspace else None
     M, N = gW.shape
+    ws_bytes = ws.numel() * 4 if workspace else 0
+    if workspace == TWO_SPLITS:
+        ws_bytes = 2 * ((N + 255) // 256 * M + M * N) * 4
+        assert ws_bytes <= ws.numel() * 4
     nat._check(nat.lib().mmseq_gemm_wgrad(M, N, dY.shape[0], nat._p(dY), M, nat._p(X), N,
                                           nat._p(gW), N, nat._p(gb), nat.dt(dY), nat.GEMM_AUTO,
-                                          nat._p(ws), ws.numel() * 4 if workspace else 0,
+                                          nat._p(ws), ws_bytes,
                                           nat._stream()), "mmseq_gemm_wgrad")
 
 
@@ -51,7 +63,10 @@ def test_wgrad_tn(M, N, K):
     refb = b0.double() + dY.double().sum(0)
     boundW = 1e-4 * math.sqrt(K) * (1 + refW.abs().max().item())
     boundb = 1e-4 * math.sqrt(K) * (1 + refb.abs().max().item())
-    for bias, workspace in ((True, True), (False, True), (True, False)):
+    legs = [(True, True), (False, True), (True, False)]
+    if (M, N, K) in TWO_SPLIT_CASES:
+        legs.append((True, TWO_SPLITS))
+    for bias, workspace in legs:
         outs = []
         for _ in range(2):
             gW, gb = W0.clone(), (b0.clone() if bias else None)
