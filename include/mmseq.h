@@ -636,6 +636,50 @@ mmseq_status mmseq_attnpool_out(int64_t rows, int T2, int Ch, int G, const void*
 mmseq_status mmseq_attnpool_out_bwd(int P, int T2, int Ch, const void* dy, void* da,
                                     float* token_colsum, mmseq_dtype dtype, mmseq_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Row selection on activations (text+image pretraining: the PISP patch swap lxrt/modeling.py:
+ * 885-942, the MRM masking and its targets :948-1009, the labelled rows of the masked-LM head).
+ * Rows are addressed as in mmseq_rows; R_out rows of out / dout, R_in rows of in / din.
+ *  fwd: out[r][:] = keep[r] ? in[src[r]][:] : 0 for r < R_out. src int32 [R_out], its entries
+ *       unique and in [0, R_in) (an entry outside reads nothing and gives a zero row); keep uint8
+ *       [R_out] or NULL (= all kept).
+ *  bwd: din (all R_in rows) is zeroed, then din[src[r]][:] = keep[r] ? dout[r][:] : 0. src is
+ *       unique, so these are plain stores: no atomics, two calls give the same bits.
+ * A permutation (R_out == R_in), a mask (identity src + keep) and a compaction (R_out < R_in) are
+ * the same call. bf16 and fp32, 16-byte accesses: cols % 8 == 0, 16-byte aligned bases, ld and
+ * bstride multiples of 16 bytes; anything else returns MMSEQ_EUNSUPPORTED with nothing launched.
+ * ------------------------------------------------------------------------------------------ */
+mmseq_status mmseq_rows_gather_fwd(int R_out, int R_in, int cols, const void* in, mmseq_rows inl,
+                                   const int32_t* src, const uint8_t* keep, void* out,
+                                   mmseq_rows outl, mmseq_dtype dtype, mmseq_stream stream);
+mmseq_status mmseq_rows_gather_bwd(int R_out, int R_in, int cols, const void* dout,
+                                   mmseq_rows doutl, const int32_t* src, const uint8_t* keep,
+                                   void* din, mmseq_rows dinl, mmseq_dtype dtype,
+                                   mmseq_stream stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Softmax cross-entropy with mean reduction over the kept rows (the masked-LM loss,
+ * lxrt/modeling.py:2260-2266 CrossEntropyLoss(ignore_index) over BertLMPredictionHead :1157-1173):
+ * logits [M][ld] bf16 or fp32 with V <= ld valid columns (finite values), labels int64 [M].
+ * Columns >= V are never used as data, whatever they hold.
+ *  fwd: lse[r] = log sum_c exp(logits[r][c]) (online max / sum in fp32, one workgroup per row);
+ *       loss_row[r] = lse[r] - logits[r][label[r]], 0 where label[r] == ignore_index (NaN for any
+ *       other label outside [0, V): nothing is read for it); stats[0] = sum(loss_row) / count,
+ *       stats[1] = count = rows with label != ignore_index, both summed in a fixed order by one
+ *       workgroup (count 0 gives stats[0] = NaN, as the reference's 0 / 0).
+ *  bwd: logits is overwritten IN PLACE, in its dtype, by dlogits[r][c] = (exp(x - lse[r]) -
+ *       (c == label[r])) * g[0] / count (g: one device float, NULL = 1); exact zeros in ignored
+ *       rows and in columns V .. ld-1, so the buffer is the A operand of the dgrad GEMM (K = ld)
+ *       and of the weight-gradient GEMM as it stands.
+ * ld % (16 bytes) == 0, ld >= V, 16-byte aligned logits; else MMSEQ_EUNSUPPORTED.
+ * ------------------------------------------------------------------------------------------ */
+mmseq_status mmseq_xent_fwd(int M, int V, const void* logits, int64_t ld, const int64_t* labels,
+                            int64_t ignore_index, float* lse, float* loss_row, float* stats,
+                            mmseq_dtype dtype, mmseq_stream stream);
+mmseq_status mmseq_xent_bwd(int M, int V, void* logits, int64_t ld, const int64_t* labels,
+                            int64_t ignore_index, const float* lse, const float* stats,
+                            const float* g, mmseq_dtype dtype, mmseq_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,14 @@ _SIGS = {
     "mmseq_image_resize_workspace": (ctypes.c_int64, [ctypes.c_int, _vp, ctypes.c_int]),
     "mmseq_image_resize_normalize": (ctypes.c_int, [ctypes.c_int, _vp, _vp] + [ctypes.c_int] * 4 +
                                      [_vp, _vp, _vp, _c_i64, _vp, _vp]),
+    "mmseq_rows_gather_fwd": (ctypes.c_int, [ctypes.c_int] * 3 + [_vp, Rows, _vp, _vp, _vp, Rows,
+                                                                  ctypes.c_int, _vp]),
+    "mmseq_rows_gather_bwd": (ctypes.c_int, [ctypes.c_int] * 3 + [_vp, Rows, _vp, _vp, _vp, Rows,
+                                                                  ctypes.c_int, _vp]),
+    "mmseq_xent_fwd": (ctypes.c_int, [ctypes.c_int] * 2 + [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp,
+                                                           ctypes.c_int, _vp]),
+    "mmseq_xent_bwd": (ctypes.c_int, [ctypes.c_int] * 2 + [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp,
+                                                           ctypes.c_int, _vp]),
 }
 
 EXPORTS = sorted(k for k in _SIGS)
@@ -283,13 +291,16 @@ def gemm(A, B, C, M, N, K, *, trans=0, lda=None, ldb=None, ldc=None, batch=1, sA
                             ws.numel() * 4, _stream()), "mmseq_gemm")
 
 
-def gemm_wgrad(dy, x, gW, gb=None):
-    """gW[out][in] += dy^T x and gb[out] += column sums of dy (fp32), dy [R][out], x [R][in]."""
+def gemm_wgrad(dy, x, gW, gb=None, lddy=None):
+    """gW[out][in] += dy^T x and gb[out] += column sums of dy (fp32), dy [R][out], x [R][in]. With
+    lddy, dy is [R][>= out] with that row stride (a column range of a wider, row-padded buffer)."""
     _dev(dy, x, gW)
     ws = gemm_workspace(dy.device)
     M, Nn = gW.shape
-    R = dy.numel() // dy.shape[-1]
-    _check(lib().mmseq_gemm_wgrad(M, Nn, R, _p(dy), dy.shape[-1], _p(x), x.shape[-1], _p(gW), Nn,
+    R = x.numel() // x.shape[-1]
+    if lddy is None:
+        lddy = dy.shape[-1]
+    _check(lib().mmseq_gemm_wgrad(M, Nn, R, _p(dy), lddy, _p(x), x.shape[-1], _p(gW), Nn,
                                   _p(gb), dt(dy), _sel["gemm"], ws.data_ptr(), ws.numel() * 4,
                                   _stream()), "mmseq_gemm_wgrad")
 
@@ -653,6 +664,101 @@ def beam_search(doc, okey, hist, h0, c0, weights, W, order, score, workspace):
     if st != EUNSUPPORTED:
         _check(st, "mmseq_beam_search")
     return st
+
+
+class Unsupported(NativeError):
+    """An entry point returned MMSEQ_EUNSUPPORTED: nothing was launched."""
+    status = EUNSUPPORTED
+
+
+def _check_shape(st, what):
+    if st == EUNSUPPORTED:
+        raise Unsupported(f"{what}: unsupported shape: {lib().mmseq_last_error().decode()}")
+    _check(st, what)
+
+
+def _gather_args(what, big, small, src, keep):
+    """big [R_in][cols] or [P][rpb][cols] (R_in = P * rpb, any row / batch strides: mmseq_rows) and
+    small [R_out][cols] (any row stride): same dtype, unit inner stride; src int32 [R_out], keep
+    uint8 [R_out] or None, contiguous. -> (R_out, R_in, cols, rows of big, rows of small)."""
+    _dev(big, small, src, keep)
+    if big.dim() not in (2, 3) or small.dim() != 2 or big.shape[-1] != small.shape[1] or \
+            big.dtype != small.dtype:
+        raise ValueError(f"{what}: [R_in][cols] (or [P][rpb][cols]) and [R_out][cols] of one dtype "
+                         "expected")
+    for t in (big, small):
+        if t.shape[-1] > 1 and t.stride(-1) != 1:
+            raise ValueError(f"{what}: unit inner stride expected")
+    R_out = small.shape[0]
+    if src.dtype != torch.int32 or src.numel() != R_out or not src.is_contiguous():
+        raise ValueError(f"{what}: src must be contiguous int32 [{R_out}]")
+    if keep is not None and (keep.dtype != torch.uint8 or keep.numel() != R_out or
+                             not keep.is_contiguous()):
+        raise ValueError(f"{what}: keep must be contiguous uint8 [{R_out}]")
+    if big.dim() == 3:
+        bl = rows(big.stride(1), big.stride(0), max(big.shape[1], 1))
+        R_in = big.shape[0] * big.shape[1]
+    else:
+        bl, R_in = rows(big.stride(0)), big.shape[0]
+    return R_out, R_in, big.shape[-1], bl, rows(small.stride(0))
+
+
+def rows_gather_fwd(x, src, keep, out):
+    """out[r] = keep[r] ? x[src[r]] : 0 (mmseq_rows_gather_fwd); x [R_in][cols] or [P][rpb][cols],
+    out [R_out][cols]. src entries must be unique and in [0, R_in). Raises Unsupported unless
+    cols % 8 == 0 and the rows are 16-byte aligned."""
+    R_out, R_in, cols, xl, ol = _gather_args("rows_gather_fwd", x, out, src, keep)
+    _check_shape(lib().mmseq_rows_gather_fwd(R_out, R_in, cols, _p(x), xl, _p(src), _p(keep),
+                                             _p(out), ol, dt(x), _stream()),
+                 "mmseq_rows_gather_fwd")
+
+
+def rows_gather_bwd(dout, src, keep, din):
+    """din = 0, then din[src[r]] = keep[r] ? dout[r] : 0 (mmseq_rows_gather_bwd); din shaped as the
+    forward's x, dout as its out."""
+    R_out, R_in, cols, dl, ol = _gather_args("rows_gather_bwd", din, dout, src, keep)
+    _check_shape(lib().mmseq_rows_gather_bwd(R_out, R_in, cols, _p(dout), ol, _p(src), _p(keep),
+                                             _p(din), dl, dt(din), _stream()),
+                 "mmseq_rows_gather_bwd")
+
+
+def _xent_args(what, logits, V, labels, lse, stats):
+    """logits: contiguous [M][ld], the first V columns data (the kernels touch whole 16-byte chunks
+    of a row and the backward writes all ld columns, so ld is the tensor's width, not a stride)."""
+    _dev(logits, labels, lse, stats)
+    if logits.dim() != 2 or not logits.is_contiguous():
+        raise ValueError(f"{what}: contiguous logits [M][ld] expected")
+    M, ld = logits.shape
+    if not 1 <= V <= ld:
+        raise ValueError(f"{what}: V = {V} outside the {ld} columns of logits")
+    if labels.dtype != torch.int64 or labels.numel() != M or not labels.is_contiguous():
+        raise ValueError(f"{what}: labels must be contiguous int64 [{M}]")
+    for t, n, name in ((lse, M, "lse"), (stats, 2, "stats")):
+        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous f32 [{n}]")
+    return M, ld
+
+
+def xent_fwd(logits, V, labels, ignore_index, lse, loss_row, stats):
+    """Cross-entropy forward (mmseq_xent_fwd): lse / loss_row f32 [M], stats f32 [2] = (mean loss
+    over the rows with label != ignore_index, their count)."""
+    M, ld = _xent_args("xent_fwd", logits, V, labels, lse, stats)
+    _dev(loss_row)
+    if loss_row.dtype != torch.float32 or loss_row.numel() != M or not loss_row.is_contiguous():
+        raise ValueError(f"xent_fwd: loss_row must be contiguous f32 [{M}]")
+    _check_shape(lib().mmseq_xent_fwd(M, V, _p(logits), ld, _p(labels), ignore_index, _p(lse),
+                                      _p(loss_row), _p(stats), dt(logits), _stream()),
+                 "mmseq_xent_fwd")
+
+
+def xent_bwd(logits, V, labels, ignore_index, lse, stats, g=None):
+    """logits <- dlogits in place, zeros in ignored rows and in the columns >= V (mmseq_xent_bwd);
+    g: the upstream gradient, one f32 on the device, or None for 1."""
+    M, ld = _xent_args("xent_bwd", logits, V, labels, lse, stats)
+    if g is not None and (g.dtype != torch.float32 or g.numel() != 1 or not g.is_cuda):
+        raise ValueError("xent_bwd: g must be one f32 on the device")
+    _check_shape(lib().mmseq_xent_bwd(M, V, _p(logits), ld, _p(labels), ignore_index, _p(lse),
+                                      _p(stats), _p(g), dt(logits), _stream()), "mmseq_xent_bwd")
 
 
 class MXFP8:

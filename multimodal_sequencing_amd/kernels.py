@@ -1124,3 +1124,128 @@ class PointerFn(torch.autograd.Function):
                       target, dnll.contiguous(), dq, dkey, dokey, store.g(wname).view(-1),
                       store.g(bname))
         return dq, dkey, dokey, None, None, None, None, None, None, None
+
+
+# ================================================================================================
+# text+image pretraining: row selection and the masked-LM loss over the labelled rows
+# ================================================================================================
+class RowsGatherFn(torch.autograd.Function):
+    """out[r] = keep[r] ? x[src[r]] : 0 (mmseq_rows_gather_fwd / _bwd): x [R_in][cols] or
+    [P][rpb][cols] with any row / batch strides (a view is read in place), src int32 [R_out] with unique entries in [0, R_in), keep uint8 [R_out] or None. One
+    Function for the PISP patch swap (a permutation), the MRM masking (identity src + keep) and the
+    compaction of the labelled rows (R_out < R_in)."""
+
+    @staticmethod
+    def forward(ctx, x, src, keep=None):
+        out = torch.empty(src.numel(), x.shape[-1], device=x.device, dtype=x.dtype)
+        N.rows_gather_fwd(x, src, keep, out)
+        ctx.save_for_backward(src, keep)
+        ctx.x_shape = tuple(x.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        src, keep = ctx.saved_tensors
+        dout = dout.contiguous()
+        din = torch.empty(ctx.x_shape, device=dout.device, dtype=dout.dtype)
+        N.rows_gather_bwd(dout, src, keep, din)
+        return din, None, None
+
+
+def _decoder_wt(store, wname):
+    """The tied decoder's dgrad operand: the word table transposed, [H][ld] in the compute dtype with
+    ld = vocab rounded up to 64 and zeros in the padding columns (K = ld of the dgrad GEMM, which
+    takes the loss kernel's row-padded dlogits as they are). Rebuilt once per store version."""
+    W = store.w(wname)
+    V, H = W.shape
+    ld = (V + 63) // 64 * 64
+    hit = getattr(store, "_decoder_wt", None)
+    if hit is None or hit[0] != (store.version, wname, W.dtype):
+        wt = hit[1] if hit is not None and hit[1].shape == (H, ld) and hit[1].dtype == W.dtype \
+            else torch.zeros(H, ld, device=W.device, dtype=W.dtype)
+        wt[:, :V].copy_(W.t())
+        hit = store._decoder_wt = ((store.version, wname, W.dtype), wt)
+    return hit[1]
+
+
+class VocabXentFn(torch.autograd.Function):
+    """mean over the kept rows of CrossEntropy(h W^T + b, labels) for the tied LM decoder
+    (lxrt/modeling.py:1164-1173, :2260-2266): the decoder GEMM writes a row-padded logit buffer
+    (ld = vocab rounded up to 64), mmseq_xent_fwd reduces it to the loss, mmseq_xent_bwd turns the
+    same buffer into dlogits in place, and that buffer is the operand of the NT dgrad GEMM (K = ld)
+    and of the TN weight-gradient GEMM, whose result accumulates into the WORD-EMBEDDING gradient
+    (the weight is tied) with the bias gradient fused. No [rows][vocab] probabilities are stored
+    and no float atomics run: two calls give the same bits. backward() consumes the saved logits,
+    so it runs once per forward."""
+
+    @staticmethod
+    def forward(ctx, h, anchor, wstore, wname, bstore, bname, labels, ignore_index):
+        h = h.contiguous()
+        Mc, H = h.shape
+        W = wstore.w(wname)
+        V = W.shape[0]
+        ld = (V + 63) // 64 * 64
+        logits = torch.empty(Mc, ld, device=h.device, dtype=h.dtype)
+        N.gemm(h, W, logits, Mc, V, H, ldc=ld, bias=bstore.f32(bname))
+        lse = torch.empty(Mc, device=h.device)
+        loss_row = torch.empty(Mc, device=h.device)
+        stats = torch.empty(2, device=h.device)
+        labels = labels.contiguous()
+        N.xent_fwd(logits, V, labels, ignore_index, lse, loss_row, stats)
+        ctx.save_for_backward(h, logits, labels, lse, stats)
+        ctx.meta = (wstore, wname, bstore, bname, ignore_index, V)
+        ctx.done = False
+        ctx.mark_non_differentiable(lse)
+        return stats[0].clone(), lse
+
+    @staticmethod
+    def backward(ctx, g, _dlse):
+        h, dl, labels, lse, stats = ctx.saved_tensors
+        wstore, wname, bstore, bname, ignore_index, V = ctx.meta
+        if ctx.done:
+            raise RuntimeError("VocabXentFn.backward ran twice: it overwrites the saved logits")
+        ctx.done = True
+        N.xent_bwd(dl, V, labels, ignore_index, lse, stats, g.reshape(1).float().contiguous())
+        Mc, ld = dl.shape
+        gW, gb = wstore.g(wname), bstore.g(bname)
+        # the bf16 TN kernel takes row counts that are multiples of 8: the odd tail of the vocabulary
+        # (50265 = 8 * 6283 + 1) is a second, tiny call on the last rows of the table
+        V8 = V // 8 * 8 if dl.dtype == torch.bfloat16 and 0 < V // 8 * 8 < V else V
+        if Mc:
+            N.gemm_wgrad(dl, h, gW[:V8], gb[:V8], lddy=ld)
+            if V8 < V:
+                N.gemm_wgrad(dl[:, V8:], h, gW[V8:], gb[V8:], lddy=ld)
+        dh = None
+        if ctx.needs_input_grad[0]:
+            dh = torch.empty_like(h)
+            N.gemm(dl, _decoder_wt(wstore, wname), dh, Mc, h.shape[1], ld)
+        return dh, None, None, None, None, None, None, None
+
+
+def labelled_rows(labels, ignore_index, device):
+    """(src int32 [M] on `device`, labels int64 [M] on `device`) of the rows with a label. The row
+    count is the decoder GEMM's M: host labels give it for free, device labels cost the one
+    read-back of torch.nonzero per step."""
+    flat = labels.reshape(-1)
+    src = torch.nonzero(flat != ignore_index).view(-1)
+    return src.to(device, torch.int32), flat[src].to(device, torch.int64)
+
+
+class MlmLossFn:
+    """The masked-LM term on the labelled rows only (ignored rows have exactly zero loss and
+    gradient): compaction of lang_output's labelled rows (RowsGatherFn), cls.predictions.transform
+    (dense + erf-GELU + LayerNorm 1e-12), tied decoder + cls.predictions.bias and the fused loss
+    (VocabXentFn). With no labelled row the result is 0 / 0 = NaN, as the reference's."""
+
+    @staticmethod
+    def apply(lang_output, labels, ignore_index, anchor, head_store, word_store,
+              wname="embeddings.word_embeddings.weight", prefix="cls.predictions."):
+        x = lang_output  # [rows][H] or [P][Lt][H], e.g. the text rows of the joint buffer, in place
+        src, lab = labelled_rows(labels, ignore_index, x.device)
+        hc = RowsGatherFn.apply(x, src, None)
+        t = LinearFn.apply(hc, anchor, head_store, prefix + "transform.dense.weight",
+                           prefix + "transform.dense.bias", GELU)
+        t = LayerNormFn.apply(t, anchor, head_store, prefix + "transform.LayerNorm", 1e-12)
+        loss, _ = VocabXentFn.apply(t, anchor, word_store, wname, head_store, prefix + "bias", lab,
+                                    ignore_index)
+        return loss

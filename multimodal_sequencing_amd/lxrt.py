@@ -52,7 +52,8 @@ class LXRTConfig(JsonConfigMixin, SimpleNamespace):
                          attention_probs_dropout_prob=attention_probs_dropout_prob, **kw)
 
 
-def _lxrt_specs(cfg, vision, text_part, max_story_length, pos_num=25, img_part=False):
+def _lxrt_specs(cfg, vision, text_part, max_story_length, pos_num=25, img_part=False,
+                image_swapping=False):
     H, I = cfg.hidden_size, cfg.intermediate_size
     std = cfg.initializer_range
     sp = [Spec("embeddings.word_embeddings.weight", (cfg.vocab_size, H), normal(std)),
@@ -116,6 +117,8 @@ def _lxrt_specs(cfg, vision, text_part, max_story_length, pos_num=25, img_part=F
                Spec("encoder.visual_token_type.token_type_embedding.weight",
                     (5, E), normal(std))]  # hard-coded max_story_length = 5 (lxrt:666-667)
     sp += linear_specs("pooler.dense", H, H, std=std)
+    if image_swapping:  # the inner model's own copy of the ISP head (lxrt:1484-1486; never applied)
+        sp += linear_specs("image_swapping_mlp", H, 2, std=std, transpose=False)
     return sp
 
 
@@ -149,7 +152,9 @@ class LXRTModel(nn.Module):
         self.vision = dict(vision or CLIP_VISION[clip_model_name])
         self.img_len = 2  # VISUAL_CONFIG.max_subsample_image_length for BERSON input (lxrt:770)
         specs = _lxrt_specs(config, self.vision, multimodal_text_part, max_story_length,
-                            img_part=multimodal_img_part)
+                            img_part=multimodal_img_part,
+                            image_swapping="image_swapping" in
+                            (kw.get("multimodal_pretrain_objectives") or ()))
         self.store = ParamStore(specs, device, compute_dtype)
         self.store.init_weights(seed=kw.get("seed", 0))
         from .resnet import rn50_attach_order
@@ -261,8 +266,10 @@ class LXRTModel(nn.Module):
         return K.VitProjFn.apply(h, self._anchor, self.proj_refs), Tv
 
     def encode_joint(self, input_ids, attention_mask, token_type_ids=None, images=None,
-                     pairs_list=None, drops=None, text_rows=False):
-        """Run embeddings (+ ViT + visn_fc) and the joint BERT stack.
+                     pairs_list=None, drops=None, text_rows=False, visual_row_op=None):
+        """Run embeddings (+ ViT + visn_fc) and the joint BERT stack. visual_row_op (vout
+        [P*Tv][E], Tv) -> [P*Tv][E]: a row operation on the ViT output before visn_fc (the
+        pretraining objectives' patch swap / masking, lxrt:885-1009); absent, nothing changes.
         Returns the joint activation [P][T][H] (compute dtype) and Lt. text_rows=True (the caller
         keeps only lang_feats, as BertForOrdering.encode, modeling_bert.py:1289-1290): the last
         layer may run on the text rows only (BertLayerFn Tq, where rows_ok), and the activation
@@ -281,6 +288,8 @@ class LXRTModel(nn.Module):
         vout, Tv = None, 0
         if not self.text_part and images is not None:
             vout, Tv = self.visual_forward(images, pairs_list)
+            if visual_row_op is not None:
+                vout = visual_row_op(vout, Tv)
         T = Lt + Tv
         x, key_bias = K.JointInputFn.apply(vout, input_ids.contiguous(), token_type_ids.contiguous(),
                                            attention_mask, self._anchor, self.input_refs, P, Lt,

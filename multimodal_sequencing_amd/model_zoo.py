@@ -81,3 +81,17 @@ def build_from_golden(cfg, device="cuda", dtype=torch.float32):
     H = cfg["head"]
     return build(joint, vision, cfg["N"], cfg["per_seq"], ff=H["ff"], heads=H["heads"],
                  inter_layers=H["layers"], text_only=cfg["text_only"], device=device, dtype=dtype)
+
+
+def build_pretrain_mm_from_golden(cfg, objectives, device="cuda", dtype=torch.float32):
+    """LXRTPretraining of the text+image stage matching a tests/golden pretrain_mm_* fixture
+    config (make_golden_pretrain_mm.py: type vocab 2, mlm_ignore_index -100)."""
+    from .pretraining import build_pretrain_mm
+    J, V = cfg["joint"], cfg["vit"]
+    joint = dict(vocab_size=J["vocab"], hidden_size=J["hidden"], num_hidden_layers=J["layers"],
+                 num_attention_heads=J["heads"], intermediate_size=J["inter"],
+                 max_position_embeddings=J["max_pos"], type_vocab_size=2)
+    vision = dict(width=V["width"], layers=V["layers"], patch=V["patch"], res=V["res"],
+                  embed=V["embed"])
+    return build_pretrain_mm(device=device, dtype=dtype, vision=vision, joint=joint,
+                             objectives=objectives, N=cfg["N"])

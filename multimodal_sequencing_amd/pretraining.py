@@ -1,5 +1,7 @@
-"""Image-only MRM pretraining (BASELINE config 2): LXRTPretraining with multimodal_img_part and
-the patch_based_mrm_classification objective.
+"""Pretraining: LXRTPretraining for the image-only MRM stage (BASELINE config 2,
+multimodal_img_part with the patch_based_mrm_classification objective, described first) and for
+the text+image stage that follows it (multimodal_img_part = multimodal_text_part = False, the
+section "Text+image stage" below).
 
 Drop-in for models/CLIP/src/lxrt/modeling.py LXRTPretraining (:1601-1734 construction,
 :1734-2484 forward) on the path trainers/run_pretraining.py runs for
@@ -28,6 +30,25 @@ zeroed BEFORE visn_fc and only those positions (and the detached targets) enter 
 loss's gradient with respect to the ViT is identically zero (the reference's autograd still runs
 the ViT backward on zeros; the fixture's ViT gradients are all 0). The ViT output therefore enters
 visn_fc detached, and the ViT parameters receive their exact (zero) gradient without the pass.
+
+Text+image stage (scripts/wikihow_pretrain.sh). Per batch ONE objective is
+drawn (:1817) from the subset of image_swapping (ISP), patch_based_image_swapping (PISP) and
+patch_based_mrm_classification (MRM) the model was built with, and the masked-LM term is added:
+  * 2 of the N steps are sub-sampled, images by index and their tokens / mask / types / labels by
+    `subsample_text` on the host (:1979-2032);
+  * ISP (:2034-2053): rand() > 0.5 "swaps" the two images, label 0 (the reference keeps a view of
+    one image while overwriting it, so a swapped story holds the first image twice), else label
+    1; loss CrossEntropy(image_swapping_mlp(pooled));
+  * PISP (:885-942): a row permutation of the ViT output (kernels.RowsGatherFn) before visn_fc;
+  * MRM (:948-1009, :2309-2351): as above, except that the masked rows are zeroed by the row
+    kernel's keep mask (every other row keeps its gradient into the ViT) and the masked outputs
+    are the joint encoder's visual rows;
+  * encoder: LXRTModel.encode_joint(visual_row_op=...); ISP / PISP use only the text rows and
+    the pooled output, so the last layer runs on the text rows;
+  * MLM (:2423-2428): kernels.MlmLossFn on the labelled rows only; the tied decoder's weight
+    gradient accumulates into the word-embedding gradient.
+`draw_mm` makes every np.random call of the reference in its order (the fixtures record the
+stream); total = objective + MLM, losses = [[objective, mlm]].
 """
 import copy
 from types import SimpleNamespace
@@ -64,6 +85,61 @@ def _pretrain_head_specs(H, vocab, std=0.02, num_answers=2):
     return sp
 
 
+ISP, PISP, MRM = "image_swapping", "patch_based_image_swapping", "patch_based_mrm_classification"
+MM_OBJECTIVES = (ISP, PISP, MRM)  # the reference's constructor order (:1647-1657, :1704-1714)
+
+
+def _mm_head_specs(H, vocab, objectives, std=0.02, num_answers=2):
+    """Heads of the text+image stage: the objectives' own (in the reference's constructor order),
+    then BertPreTrainingHeads, the object head and the answer head as in config 2."""
+    sp = []
+    if ISP in objectives:
+        sp += linear_specs("image_swapping_mlp", H, 2, std=std)
+    if PISP in objectives:
+        sp += linear_specs("patch_based_image_swapping_mlp", H, 2, std=std)
+    base = _pretrain_head_specs(H, vocab, std, num_answers)
+    m = "patch_based_mrm_classification_head."
+    if MRM in objectives:
+        sp += [x for x in base if x.name.startswith(m)]
+    return sp + [x for x in base if not x.name.startswith(m)]
+
+
+def subsample_text(input_ids, attention_mask, token_type_ids, masked_lm_labels, sub_idx, n_steps,
+                   cls_id, pad_id, ignore_index):
+    """The text of the sub-sampled steps (:1986-2032), on the host: step k of a story runs from its
+    k-th cls token to the next one (the last step: L // n_steps tokens); the kept steps are
+    concatenated and padded to L // n_steps * 2 with pad_id / 0 / 0 / ignore_index.
+    All tensors int64 [B][L] (token_type_ids may be None); sub_idx [B][2] ascending. Returns
+    (input_ids, attention_mask, token_type_ids or None, masked_lm_labels), each [B][pad]."""
+    ids = torch.as_tensor(input_ids).cpu()
+    B, L = ids.shape
+    per, n_sub = L // n_steps, len(sub_idx[0])
+    pad = per * n_sub
+    gather = torch.full((B, pad), -1, dtype=torch.int64)
+    for b in range(B):
+        cls_pos = torch.nonzero(ids[b] == cls_id).view(-1).tolist()
+        at = 0
+        for k in (int(x) for x in sub_idx[b]):
+            if k >= len(cls_pos):
+                raise ValueError(f"story {b}: step {k} of {len(cls_pos)} cls tokens")
+            start = cls_pos[k]
+            end = start + per if k == n_steps - 1 else cls_pos[k + 1]
+            if at + end - start > pad or end > L:
+                raise ValueError(f"story {b}: the sub-sampled steps exceed {pad} tokens")
+            gather[b, at:at + end - start] = torch.arange(start, end)
+            at += end - start
+    valid, idx = gather >= 0, gather.clamp(min=0)
+
+    def take(t, fill):
+        if t is None:
+            return None
+        t = torch.as_tensor(t).cpu()
+        return torch.where(valid, t.gather(1, idx), torch.full_like(idx, fill).to(t.dtype))
+
+    return (take(ids, pad_id), take(attention_mask, 0), take(token_type_ids, 0),
+            take(masked_lm_labels, ignore_index))
+
+
 class LXRTPretraining(nn.Module):
     MASK_NUM = 5  # pb_mrm_cls_mask_num (:1694)
     MRM_SCALE = 0.2  # :2347
@@ -75,8 +151,8 @@ class LXRTPretraining(nn.Module):
                  compute_dtype=torch.bfloat16, seed=0, vision=None, **kwargs):
         super().__init__()
         if not kwargs.get("multimodal_img_part", False):
-            raise NotImplementedError(
-                "only the image-only MRM pretraining path (config 2) is on the hot path")
+            self._init_mm(config, num_answers, device, compute_dtype, seed, vision, task_qa, kwargs)
+            return
         objectives = list(kwargs.get("multimodal_pretrain_objectives") or [])
         if objectives != ["patch_based_mrm_classification"]:
             raise NotImplementedError(
@@ -112,6 +188,48 @@ class LXRTPretraining(nn.Module):
         self.last_prediction_scores = None
         self.last_seq_relationship = None
 
+    def _init_mm(self, config, num_answers, device, compute_dtype, seed, vision, task_qa, kwargs):
+        """The text+image stage (scripts/wikihow_pretrain.sh): MLM + one of ISP / PISP / MRM per
+        batch over the joint encoder; multimodal_img_part = multimodal_text_part = False."""
+        objectives = list(kwargs.get("multimodal_pretrain_objectives") or [])
+        bad = [o for o in objectives if o not in MM_OBJECTIVES]
+        if bad or not objectives:
+            raise NotImplementedError(
+                f"pretraining objectives {bad or objectives}: the text+image stage builds "
+                f"{', '.join(MM_OBJECTIVES)}")
+        if kwargs.get("multimodal_text_part", False):
+            raise NotImplementedError("text-only pretraining (multimodal_text_part) is not built")
+        vis = vision if isinstance(vision, dict) else None
+        if (vis or {}).get("type") == "rn50" or str(kwargs.get("clip_model_name", "")).startswith("RN"):
+            raise NotImplementedError("RN50 as the pretraining backbone is not built (ViT only)")
+        self.config = config
+        self.multimodal_img_part = False
+        self.multimodal_pretrain_objectives = objectives
+        self.cls_id, self.sep_id = kwargs.get("cls_id", 0), kwargs.get("sep_id", 2)
+        self.pad_id = kwargs.get("pad_id", 1)
+        self.mlm_ignore_index = kwargs.get("mlm_ignore_index", -1)
+        self.max_story_length = kwargs.get("max_story_length", 5)
+        self.task_qa = task_qa
+        inner_kw = {k: v for k, v in kwargs.items()
+                    if k in ("cls_id", "sep_id", "max_story_length", "clip_model_name",
+                             "multimodal_pretrain_objectives")}
+        self.bert = LXRTModel(config, device=device, compute_dtype=compute_dtype, vision=vision,
+                              seed=seed, **inner_kw)
+        self.store = ParamStore(_mm_head_specs(config.hidden_size, config.vocab_size, objectives,
+                                               config.initializer_range, num_answers),
+                                device, compute_dtype)
+        self.store.init_weights(seed=seed + 7)
+        attach_tree(self, self.store.params)  # spec order = the reference's registration order
+        attach_tree(self, {"cls.predictions.decoder.weight":
+                           self.bert.store.params["embeddings.word_embeddings.weight"]})
+        self._anchor = torch.zeros((), device=device, requires_grad=True)
+        self.register_load_state_dict_post_hook(_mark_stale)
+        self.rng = np.random.RandomState(seed)
+        self.device_ = torch.device(device)
+        self.last_objective = None
+        self.last_objective_logits = self.last_objective_labels = None
+        self.last_pooled = self.last_mrm_targets = None
+
     def stores(self):
         return [self.bert.store, self.store]
 
@@ -121,7 +239,11 @@ class LXRTPretraining(nn.Module):
 
     def ddp_units(self):
         """(units, begin_stores) for trainer.GradAllReduce: the heads and visn_fc finish together;
-        no per-layer units (the ViT gradient is exactly zero, see the module docstring)."""
+        no per-layer units (the ViT gradient is exactly zero, see the module docstring). The
+        text+image stage: the inner model's per-layer spans, the head store completing as a whole
+        before the inner model's backward begins (as BertForOrdering.ddp_units)."""
+        if not self.multimodal_img_part:
+            return {id(self.bert.store): self.bert.grad_units()}, [self.store]
         return {}, []
 
     # ------------------------------------------------------------------------------------
@@ -145,6 +267,72 @@ class LXRTPretraining(nn.Module):
         return {"sub_idx": np.asarray(sub_idx, np.int64), "mask_idx": np.asarray(mask_idx, np.int64),
                 "shuffle": np.asarray(shuffle, np.int64)}
 
+    def draw_mm(self, B, N, Tv, rng=None):
+        """The reference's np.random draws of one text+image batch, in its call order and
+        distributions: the objective (:1817), 2 of N images per story (:1981), then the
+        objective's own. ISP (:2038-2050): rand() > 0.5 swaps. PISP (:889-939): the two patch ranges
+        are [0, 1 + g^2) (the class token included) and [1 + g^2, 1 + 2 g^2); a count in
+        [0, g^2) per story, preceded by one that is overwritten; per range one selection that is
+        used and one that is not; then rand() > 0.5 swaps the selections row for row
+        (`patch_src`: the row of the ViT output each row is taken from). MRM (:983-990, :2322):
+        as config 2, with the redraw while more than 60 % of a selection repeats the one before."""
+        rng = rng or self.rng
+        d = {"objective": str(rng.choice(self.multimodal_pretrain_objectives, 1, replace=False)[0])}
+        d["sub_idx"] = np.asarray([sorted(rng.choice(N, 2, replace=False)) for _ in range(B)],
+                                  np.int64)
+        obj = d["objective"]
+
+        def swapped():
+            if rng.rand() > 0.5:
+                rng.choice(2, 2, replace=False)  # always the pair (0, 1) once sorted
+                return 1
+            return 0
+
+        if obj == ISP:
+            d["swap"] = np.asarray([swapped() for _ in range(B)], np.uint8)
+        elif obj == PISP:
+            patch_len = Tv // 2
+            ranges = [list(range(0, 1 + patch_len)), list(range(1 + patch_len, Tv))]
+            rng.randint(0, patch_len)
+            count, sel = [], []
+            for _ in range(B):
+                count.append(int(rng.randint(0, patch_len)))
+                cur = []
+                for r in ranges:
+                    cur.append(np.asarray(rng.choice(r, count[-1], replace=False), np.int64))
+                    rng.choice(r, count[-1], replace=False)
+                sel.append(cur)
+            d["count"] = np.asarray(count, np.int64)
+            d["swap"] = np.asarray([swapped() for _ in range(B)], np.uint8)
+            src = np.tile(np.arange(Tv, dtype=np.int64), (B, 1))
+            for b in range(B):
+                if d["swap"][b]:
+                    x, y = sel[b]
+                    src[b, y], src[b, x] = x, y
+            d["patch_src"] = src
+        else:
+            per = Tv // 2
+            masks = []
+            for _ in range(B):
+                m, prev = [], None
+                for start in range(1, Tv, per):
+                    choices = list(range(start, start + per))
+                    cur = rng.choice(choices, self.MASK_NUM, replace=False)
+                    while prev is not None and \
+                            sum(int(x) in set(int(p) for p in prev) for x in cur) / len(cur) > 0.6:
+                        cur = rng.choice(choices, self.MASK_NUM, replace=False)
+                    prev = cur
+                    m += sorted(int(x) for x in cur)
+                masks.append(m)
+            d["mask_idx"] = np.asarray(masks, np.int64)
+            sh = []
+            for _ in range(B):
+                idx = np.arange(self.MASK_NUM * 2)
+                rng.shuffle(idx)
+                sh.append(np.asarray(idx, np.int64))
+            d["shuffle"] = np.asarray(sh, np.int64)
+        return d
+
     def _lin(self, x, store, name, act=0, bias=True):
         return K.LinearFn.apply(x, self._anchor, store, name + ".weight",
                                 name + ".bias" if bias else None, act)
@@ -162,6 +350,13 @@ class LXRTPretraining(nn.Module):
             batch = input_ids
             visual_feats = batch.get("images")
             draws = batch.get("draws", draws)
+            if not self.multimodal_img_part:
+                input_ids, token_type_ids = batch.get("input_ids"), batch.get("token_type_ids")
+                attention_mask = batch.get("attention_mask")
+                masked_lm_labels = batch.get("masked_lm_labels")
+        if not self.multimodal_img_part:
+            return self._forward_mm(input_ids, token_type_ids, attention_mask, masked_lm_labels,
+                                    visual_feats, draws)
         images = visual_feats.to(self.device_, torch.float32).contiguous()
         B, Nimg = images.shape[:2]
         inner = self.bert
@@ -228,6 +423,112 @@ class LXRTPretraining(nn.Module):
         losses = mrm.detach().view(1, 1)
         return mrm, losses, answer.detach()
 
+    def _forward_mm(self, input_ids, token_type_ids, attention_mask, masked_lm_labels, images,
+                    draws):
+        """:1734-2484 for the text+image stage: one objective per batch + the masked-LM term.
+        Returns (total_loss, [[objective_loss, mlm_loss]], answer_score)."""
+        if masked_lm_labels is None or images is None:
+            raise ValueError("the text+image stage needs masked_lm_labels and images")
+        dev = self.device_
+        images = images.to(dev, torch.float32).contiguous()
+        B, Nimg = images.shape[:2]
+        inner = self.bert
+        st_in, st = inner.store, self.store
+        for s in self.stores():
+            if s.shadow_stale:
+                s.refresh_shadows()
+        g = images.shape[-1] // inner.vision["patch"]
+        Tv = 1 + 2 * g * g
+        if draws is None:
+            draws = self.draw_mm(B, Nimg, Tv)
+        obj = str(np.asarray(draws["objective"]).reshape(-1)[0])
+        if obj not in self.multimodal_pretrain_objectives:
+            raise ValueError(f"objective {obj} was not built into this model")
+        self.last_objective = obj
+        sub_idx = np.asarray(draws["sub_idx"], np.int64)
+        if attention_mask is None:
+            attention_mask = torch.ones_like(torch.as_tensor(input_ids))
+        # sub-sampling: integer work on the host, the images are only indexed (mmseq_vit_im2col)
+        ids, mask, tt, labels = subsample_text(input_ids, attention_mask, token_type_ids,
+                                               masked_lm_labels, sub_idx, Nimg, self.cls_id,
+                                               self.pad_id, self.mlm_ignore_index)
+        pairs = torch.as_tensor(sub_idx).clone()
+        if obj == ISP:
+            # :2042-2046 keeps a VIEW of image y while overwriting it, so a "swapped" story holds
+            # image x twice (the fixtures record it)
+            swap = torch.as_tensor(np.asarray(draws["swap"]).astype(bool))
+            pairs[:, 1] = torch.where(swap, pairs[:, 0], pairs[:, 1])
+            obj_labels = (~swap).long()
+        elif obj == PISP:
+            obj_labels = (~torch.as_tensor(np.asarray(draws["swap"]).astype(bool))).long()
+        pairs = pairs.to(dev).view(B, 1, 2).contiguous()
+        row_op, mask_rows = None, None
+        base = torch.arange(B, dtype=torch.int64)[:, None] * Tv
+        if obj == PISP:
+            src = (base + torch.as_tensor(np.asarray(draws["patch_src"], np.int64))).view(-1)
+            src = src.to(dev, torch.int32)
+            row_op = lambda vout, _tv: K.RowsGatherFn.apply(vout, src, None)  # noqa: E731
+        elif obj == MRM:
+            mask_idx = torch.as_tensor(np.asarray(draws["mask_idx"], np.int64))
+            nm = mask_idx.shape[1]
+            mask_rows = (base + mask_idx).view(-1)
+            keep = torch.ones(B * Tv, dtype=torch.uint8)
+            keep[mask_rows] = 0
+            keep = keep.to(dev)
+            ident = torch.arange(B * Tv, dtype=torch.int32, device=dev)
+            gt_rows = mask_rows.to(dev, torch.int32)
+            stash = {}
+
+            def row_op(vout, _tv):
+                # targets: the (detached) features at the masked patches; the sequence fed on has
+                # those rows zeroed, every other row keeps its gradient into the ViT
+                stash["gt"] = K.RowsGatherFn.apply(vout.detach(), gt_rows, None)
+                return K.RowsGatherFn.apply(vout, ident, keep)
+        D = inner.new_dropouts()
+        ph = self.config.hidden_dropout_prob
+        joint, Lt = inner.encode_joint(ids.to(dev), mask.to(dev),
+                                       None if tt is None else tt.to(dev), images, pairs, drops=D,
+                                       text_rows=obj != MRM, visual_row_op=row_op)
+        H = joint.shape[-1]
+        lang = joint[:, :Lt]
+        # pooler (:1125-1137): dense(lang[:, 0]), no tanh
+        pooled = self._lin(lang[:, 0].contiguous(), st_in, "pooler.dense")
+        self.last_pooled = pooled.detach()
+        a = "answer_head.logit_fc."
+        answer = self._lin(self._ln(self._lin(pooled, st, a + "0", act=K.GELU), st, a + "2"),
+                           st, a + "3")
+        if obj == MRM:
+            vf = "encoder.visn_fc."
+            targets = K.dropout(self._ln(self._lin(stash["gt"], st_in, vf + "visn_fc"), st_in,
+                                         vf + "visn_layer_norm"), D.site(ph, "pt_visn_fc_gt"))
+            targets = targets.view(B, nm, H)
+            self.last_mrm_targets = targets.detach()
+            T = joint.shape[1]
+            out_rows = (torch.arange(B, dtype=torch.int64)[:, None] * T + Lt + mask_idx).view(-1)
+            masked = K.RowsGatherFn.apply(joint, out_rows.to(dev, torch.int32), None).view(B, nm, H)
+            shuffle = np.asarray(draws["shuffle"], dtype=np.int64)
+            bidx = torch.arange(B, device=dev)[:, None]
+            tshuf = targets[bidx, torch.as_tensor(shuffle, device=dev)]
+            qa = torch.cat([masked[:, :, None, :].expand(B, nm, nm, H),
+                            tshuf[:, None, :, :].expand(B, nm, nm, H)], -1)
+            m = "patch_based_mrm_classification_head."
+            hdn = self._ln(self._lin(qa.contiguous(), st, m + "transform.dense", act=K.GELU), st,
+                           m + "transform.LayerNorm")
+            scores = K.LinearFn.apply(hdn, self._anchor, st, m + "decoder.weight", m + "bias", 0)
+            scores = scores.view(B, nm, nm).float()
+            obj_labels = torch.as_tensor(np.argsort(shuffle, axis=1))
+            logp = torch.log_softmax(scores, -1)
+            ce = -logp.gather(-1, obj_labels.to(dev)[:, :, None]).squeeze(-1).mean(-1)
+            obj_loss = ce.sum() * self.MRM_SCALE
+        else:
+            scores = self._lin(pooled, st, obj + "_mlp").float()
+            obj_loss = torch.nn.functional.cross_entropy(scores, obj_labels.to(dev))
+        self.last_objective_logits, self.last_objective_labels = scores.detach(), obj_labels
+        mlm = K.MlmLossFn.apply(lang, labels, self.mlm_ignore_index, self._anchor, st, st_in)
+        total = obj_loss + mlm
+        losses = torch.stack([obj_loss.detach(), mlm.detach()]).view(1, 2)
+        return total, losses, answer.detach()
+
     def _lm_head(self, x):
         """BertLMPredictionHead (:1157-1173): transform (dense + erf-GELU + LN 1e-12) and the tied
         decoder + bias as one MFMA GEMM into a row-padded buffer (ld = vocab rounded up to 64)."""
@@ -256,5 +557,22 @@ def build_config2(device="cuda", dtype=torch.bfloat16, seed=0, vision="ViT-B/16"
                            multimodal_img_part=True, cls_id=0, sep_id=2, pad_id=1,
                            max_story_length=5, mlm_ignore_index=-1,
                            multimodal_pretrain_objectives=["patch_based_mrm_classification"],
+                           clip_model_name="ViT-B/16", pretraining=True, device=device,
+                           compute_dtype=dtype, seed=seed, vision=vis)
+
+
+def build_pretrain_mm(device="cuda", dtype=torch.bfloat16, seed=0, vision="ViT-B/16", joint=None,
+                      objectives=MM_OBJECTIVES, N=5):
+    """The text+image stage (scripts/wikihow_pretrain.sh): RoBERTa-base sizes (vocab 50265) around
+    a CLIP ViT-B/16, N = 5 steps of 60 tokens, MLM + ISP / PISP / MRM, mlm_ignore_index -100."""
+    from .lxrt import CLIP_VISION
+    j = dict(vocab_size=50265, hidden_size=768, num_hidden_layers=12, num_attention_heads=12,
+             intermediate_size=3072, max_position_embeddings=514, type_vocab_size=1)
+    j.update(joint or {})
+    vis = dict(vision) if isinstance(vision, dict) else dict(CLIP_VISION[vision])
+    return LXRTPretraining(LXRTConfig(**j), visual_losses="obj", multimodal_text_part=False,
+                           multimodal_img_part=False, cls_id=0, sep_id=2, pad_id=1,
+                           max_story_length=N, mlm_ignore_index=-100,
+                           multimodal_pretrain_objectives=list(objectives),
                            clip_model_name="ViT-B/16", pretraining=True, device=device,
                            compute_dtype=dtype, seed=seed, vision=vis)
