@@ -121,7 +121,8 @@ mmseq_status mmseq_gemm_wgrad(int M, int N, int K, const void* A, int64_t lda, c
  *   K at +k_off + h*64, V at +v_off + h*64. head_dim is 64.
  *   key_bias: [P][T] f32 additive (0 or -10000), or NULL.  out row: out + (p*T+t)*ld_out + h*64.
  *   lse: [P][heads][T] f32 (log-sum-exp of the scaled, biased scores), written by fwd.
- * bwd: delta workspace [P][heads][T] f32; dqkv has the same packed layout as qkv (ld_dqkv).
+ * bwd: delta workspace [P][heads][T] f32; dqkv holds dQ | dK | dV at qkv's column offsets with a
+ *   row stride of its own: max(q_off, k_off, v_off) + heads*64 <= ld_dqkv, else MMSEQ_EINVAL.
  * drop: attention-probability dropout (lxrt:421), idx = ((p*heads + h)*T + q)*Tp4 + k with the
  *   row stride Tp4 = T rounded up to a multiple of 4 (a lane's four keys 4g..4g+3 form one quad).
  * variant (per call, bf16 only): 1 = 128-row workgroups with LDS-DMA double-buffered K/V (or

@@ -1658,7 +1658,7 @@ __global__ __launch_bounds__(256, DMODE == 0 ? 4 : 2) void attn_dq_bf16_kernel(A
     Dd[grp] = dot;
     const int64_t ri = ((int64_t)p * a.heads + h) * T + q;
     L2[grp] = q < a.Tq ? L2[grp] * LOG2E : 1e30f;
-    if (q < T && g == 0) a.delta[ri] = dot;
+    if (q < a.Tq && g == 0) a.delta[ri] = dot;  // rows >= Tq stay untouched (mmseq_attn_bwd_rows)
     settle(qf[grp][0]);
     settle(qf[grp][1]);
     settle(L2[grp]);
@@ -2277,8 +2277,14 @@ static mmseq_status attn_bwd_impl(int P, int T, int Tq, int heads, const void* q
   if (st) return st;
   const int ve = dtype == MMSEQ_BF16 ? 8 : 4;
   MMSEQ_REQUIRE(out && dout && lse && delta && dqkv, "attn_bwd: null buffer");
-  MMSEQ_REQUIRE(aligned16(dout) && ld_dout % ve == 0 && ld_dqkv >= ld_qkv - 0 && ld_dqkv % 1 == 0,
-                "attn_bwd: dout alignment");
+  MMSEQ_REQUIRE(aligned16(dout) && ld_dout % ve == 0, "attn_bwd: dout alignment");
+  // dqkv holds dQ | dK | dV at qkv's column offsets with its own row stride, which may be narrower
+  // than ld_qkv as long as every head slice fits the row. The 64-row kernels store single elements
+  // (no multiple needed); the 128-row kernels store groups of four bf16 and are held to 16-byte
+  // rows below.
+  const int64_t hi_off = q_off > k_off ? (q_off > v_off ? q_off : v_off) : (k_off > v_off ? k_off : v_off);
+  MMSEQ_REQUIRE(hi_off + (int64_t)heads * 64 <= ld_dqkv,
+                "attn_bwd: head slices exceed the dqkv row (ld_dqkv=%lld)", (long long)ld_dqkv);
   MMSEQ_REQUIRE(Tq >= 1 && Tq <= T && (Tq == T || (dtype == MMSEQ_BF16 && variant && !q8)),
                 "attn_bwd: Tq=%d (1 <= Tq <= T; Tq < T needs the bf16 fast kernels, no MX-fp8 copy)", Tq);
   if (P == 0) return MMSEQ_OK;
