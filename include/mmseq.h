@@ -681,6 +681,54 @@ mmseq_status mmseq_xent_bwd(int M, int V, void* logits, int64_t ld, const int64_
                             int64_t ignore_index, const float* lse, const float* stats,
                             const float* g, mmseq_dtype dtype, mmseq_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Pretraining inputs on device (text+image stage): csrc/inputs.hip.
+ *
+ * mlm_mask: trainers/train_utils.py:19-66 mask_tokens_sentence on input_ids [B][L] IN PLACE, with
+ * labels [B][L] written. A token is a candidate iff it is neither pad_id nor cls_id (</s> is
+ * maskable, as in the reference); a candidate is selected with probability p; labels = the
+ * original id where selected, ignore_index elsewhere; of the selected 80 % become mask_id, half of
+ * the rest a word drawn uniformly from [cls_id + 1, vocab), the remainder stay. (The reference
+ * draws its Bernoulli for the first n positions, n = the number of non-pad tokens, and asserts
+ * that none of them is a pad: for trailing padding that is "the non-pad positions".)
+ * Counter-based like the dropout above, a pure function of (seed, stream_id, e = b*L + l), so the
+ * launch geometry cannot matter:
+ *   (k0, k1)   = the dropout key of (seed, stream_id) (make_drop)
+ *   h          = lowbias32(lowbias32((uint32_t)e ^ k0) + ((uint32_t)(e >> 32) ^ k1))
+ *                (TWO rounds: with one, the selection bits of elements 64 apart correlate)
+ *   h2         = drop_hash2(h); h3 = drop_hash2(h2)
+ *   selected   iff candidate and (h & 0xFFFF) < thr, thr = clamp(floor(p * 65536 + 0.5), 0, 65536)
+ *              (p = 0 selects nothing, p = 1 every candidate)
+ *   -> mask_id iff (h >> 16) < 52429; else -> random word iff (h2 & 0xFFFF) < 32768,
+ *   word       = cls_id + 1 + (((uint64_t)h3 * (uint64_t)(vocab - cls_id - 1)) >> 32)
+ * 0 <= cls_id + 1 < vocab < 2^31 and B * L < 2^31, else MMSEQ_EINVAL with nothing launched.
+ *
+ * subsample_text: the text of the n_sub sub-sampled steps per story (lxrt/modeling.py:1986-2032):
+ * step k runs from the k-th cls_id to the next one, the last step (k = n_steps - 1) takes
+ * L / n_steps tokens; the steps sub_idx[b][0 .. n_sub) (ascending) are concatenated into rows of
+ * (L / n_steps) * n_sub and padded with pad_id / 0 / 0 / ignore_index. token_type_ids and labels
+ * may be NULL together with their outputs. status[0] += the number of stories with a step index
+ * outside [0, n_steps) or without its cls token, a non-last step whose following cls token is
+ * missing, or kept steps that overrun the padded length or L (zero it first; the caller raises);
+ * such a story's output rows are all padding. One wave per story; 2 <= n_steps <= 64.
+ *
+ * rows_compact: src[0 .. count) = the r < R, ascending, with labels[r] != ignore_index, and
+ * out_labels their labels: torch.nonzero's order, so the masked-LM loss sums the same rows in the
+ * same order as with host labels. src / out_labels hold R entries; nothing at or beyond count is
+ * written; *count is a plain store. One workgroup, an ordered scan, no atomics: deterministic.
+ * ------------------------------------------------------------------------------------------ */
+mmseq_status mmseq_mlm_mask(int B, int L, int64_t* input_ids, int64_t* labels, int64_t pad_id,
+                            int64_t cls_id, int64_t mask_id, int64_t vocab, int64_t ignore_index,
+                            float p, uint64_t seed, uint32_t stream_id, mmseq_stream stream);
+mmseq_status mmseq_subsample_text(int B, int L, int n_steps, int n_sub, const int64_t* input_ids,
+                                  const int64_t* attention_mask, const int64_t* token_type_ids,
+                                  const int64_t* labels, const int64_t* sub_idx, int64_t cls_id,
+                                  int64_t pad_id, int64_t ignore_index, int64_t* out_ids,
+                                  int64_t* out_mask, int64_t* out_token_type, int64_t* out_labels,
+                                  int32_t* status, mmseq_stream stream);
+mmseq_status mmseq_rows_compact(int R, const int64_t* labels, int64_t ignore_index, int32_t* src,
+                                int64_t* out_labels, int32_t* count, mmseq_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,11 @@ _SIGS = {
                                                            ctypes.c_int, _vp]),
     "mmseq_xent_bwd": (ctypes.c_int, [ctypes.c_int] * 2 + [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp,
                                                            ctypes.c_int, _vp]),
+    "mmseq_mlm_mask": (ctypes.c_int, [ctypes.c_int] * 2 + [_vp, _vp] + [_c_i64] * 5 +
+                       [ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32, _vp]),
+    "mmseq_subsample_text": (ctypes.c_int, [ctypes.c_int] * 4 + [_vp] * 5 + [_c_i64] * 3 +
+                             [_vp] * 6),
+    "mmseq_rows_compact": (ctypes.c_int, [ctypes.c_int, _vp, _c_i64, _vp, _vp, _vp, _vp]),
 }
 
 EXPORTS = sorted(k for k in _SIGS)
@@ -759,6 +764,73 @@ def xent_bwd(logits, V, labels, ignore_index, lse, stats, g=None):
         raise ValueError("xent_bwd: g must be one f32 on the device")
     _check_shape(lib().mmseq_xent_bwd(M, V, _p(logits), ld, _p(labels), ignore_index, _p(lse),
                                       _p(stats), _p(g), dt(logits), _stream()), "mmseq_xent_bwd")
+
+
+def _i64_dev(what, name, t, shape):
+    if not torch.is_tensor(t) or t.dtype != torch.int64 or not t.is_contiguous() or \
+            tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} must be a contiguous int64 tensor {list(shape)}")
+    _dev(t)
+
+
+def mlm_mask(input_ids, labels, pad_id, cls_id, mask_id, vocab, ignore_index, p, seed, stream_id=0):
+    """mask_tokens_sentence on the device (mmseq_mlm_mask): input_ids int64 [B][L] masked in place,
+    labels int64 [B][L] written; a pure function of (seed, stream_id, element index)."""
+    if not torch.is_tensor(input_ids) or input_ids.dim() != 2:
+        raise ValueError("mlm_mask: input_ids must be a tensor [B][L]")
+    B, L = input_ids.shape
+    _i64_dev("mlm_mask", "input_ids", input_ids, (B, L))
+    _i64_dev("mlm_mask", "labels", labels, (B, L))
+    _check(lib().mmseq_mlm_mask(B, L, _p(input_ids), _p(labels), pad_id, cls_id, mask_id, vocab,
+                                ignore_index, float(p), seed & 0xFFFFFFFFFFFFFFFF,
+                                stream_id & 0xFFFFFFFF, _stream()), "mmseq_mlm_mask")
+
+
+def subsample_text(input_ids, attention_mask, token_type_ids, labels, sub_idx, n_steps, cls_id,
+                   pad_id, ignore_index, out_ids, out_mask, out_tt, out_labels, status):
+    """The text of the sub-sampled steps (mmseq_subsample_text): inputs int64 [B][L]
+    (token_type_ids / labels may be None, with their outputs), sub_idx int64 [B][n_sub], outputs
+    int64 [B][L // n_steps * n_sub]; status int32, zeroed by the caller: status[0] += bad stories."""
+    if not torch.is_tensor(input_ids) or input_ids.dim() != 2 or \
+            not torch.is_tensor(sub_idx) or sub_idx.dim() != 2:
+        raise ValueError("subsample_text: input_ids [B][L] and sub_idx [B][n_sub] expected")
+    B, L = input_ids.shape
+    n_sub = sub_idx.shape[1]
+    pad = L // n_steps * n_sub
+    _i64_dev("subsample_text", "sub_idx", sub_idx, (B, n_sub))
+    for name, t, o in (("input_ids", input_ids, out_ids), ("attention_mask", attention_mask, out_mask),
+                       ("token_type_ids", token_type_ids, out_tt), ("labels", labels, out_labels)):
+        if t is None and o is None and name in ("token_type_ids", "labels"):
+            continue
+        _i64_dev("subsample_text", name, t, (B, L))
+        _i64_dev("subsample_text", "the output of " + name, o, (B, pad))
+    if not torch.is_tensor(status) or status.dtype != torch.int32 or status.numel() < 1 or \
+            not status.is_cuda:
+        raise ValueError("subsample_text: status must be int32 on the device")
+    _check(lib().mmseq_subsample_text(B, L, n_steps, n_sub, _p(input_ids), _p(attention_mask),
+                                      _p(token_type_ids), _p(labels), _p(sub_idx), cls_id, pad_id,
+                                      ignore_index, _p(out_ids), _p(out_mask), _p(out_tt),
+                                      _p(out_labels), _p(status), _stream()),
+           "mmseq_subsample_text")
+
+
+def rows_compact(labels, ignore_index, src, out_labels, count):
+    """src int32 [R] / out_labels int64 [R]: their first count[0] entries = the rows r, ascending,
+    with labels[r] != ignore_index, and those labels (mmseq_rows_compact); labels int64 [R], count
+    int32 [1], all on the device. Nothing at or beyond count[0] is written."""
+    if not torch.is_tensor(labels) or labels.dim() != 1:
+        raise ValueError("rows_compact: labels must be a tensor [R]")
+    R = labels.numel()
+    _i64_dev("rows_compact", "labels", labels, (R,))
+    _i64_dev("rows_compact", "out_labels", out_labels, (R,))
+    for name, t, n in (("src", src, R), ("count", count, 1)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or not t.is_contiguous() or \
+                t.numel() != n or not t.is_cuda:
+            raise ValueError(f"rows_compact: {name} must be contiguous int32 [{n}] on the device")
+    if R >= 1 << 31:
+        raise ValueError("rows_compact: R must be below 2^31")
+    _check(lib().mmseq_rows_compact(R, _p(labels), ignore_index, _p(src), _p(out_labels),
+                                    _p(count), _stream()), "mmseq_rows_compact")
 
 
 class MXFP8:

@@ -1222,10 +1222,36 @@ class VocabXentFn(torch.autograd.Function):
         return dh, None, None, None, None, None, None, None
 
 
+def mlm_mask(input_ids, pad_id, cls_id, mask_id, vocab, ignore_index, p, seed, stream_id=0):
+    """Dynamic MLM masking on the device (mmseq_mlm_mask; trainers/train_utils.py:19-66):
+    input_ids int64 [B][L] is masked IN PLACE, the labels int64 [B][L] are returned. The same
+    (seed, stream_id) gives the same bits."""
+    labels = torch.empty_like(input_ids)
+    N.mlm_mask(input_ids, labels, int(pad_id), int(cls_id), int(mask_id), int(vocab),
+               int(ignore_index), float(p), int(seed), int(stream_id))
+    return labels
+
+
+def compact_rows(labels, ignore_index, count):
+    """Device labels -> (src int32 [R], labels int64 [R]) whose first count[0] entries are the
+    labelled rows in row order (mmseq_rows_compact); count: int32 [1] on the device, written by the
+    kernel and read by the caller, who slices both."""
+    flat = labels.reshape(-1).to(torch.int64).contiguous()
+    src = torch.empty(flat.numel(), dtype=torch.int32, device=flat.device)
+    lab = torch.empty_like(flat)
+    N.rows_compact(flat, int(ignore_index), src, lab, count)
+    return src, lab
+
+
 def labelled_rows(labels, ignore_index, device):
-    """(src int32 [M] on `device`, labels int64 [M] on `device`) of the rows with a label. The row
-    count is the decoder GEMM's M: host labels give it for free, device labels cost the one
-    read-back of torch.nonzero per step."""
+    """(src int32 [M] on `device`, labels int64 [M] on `device`) of the rows with a label, in row
+    order. The row count is the decoder GEMM's M: host labels give it for free, device labels run
+    the compaction kernel and read that one integer back."""
+    if labels.is_cuda:
+        count = torch.empty(1, dtype=torch.int32, device=labels.device)
+        src, lab = compact_rows(labels, ignore_index, count)
+        n = int(count.item())
+        return src[:n].to(device), lab[:n].to(device)
     flat = labels.reshape(-1)
     src = torch.nonzero(flat != ignore_index).view(-1)
     return src.to(device, torch.int32), flat[src].to(device, torch.int64)
@@ -1235,13 +1261,15 @@ class MlmLossFn:
     """The masked-LM term on the labelled rows only (ignored rows have exactly zero loss and
     gradient): compaction of lang_output's labelled rows (RowsGatherFn), cls.predictions.transform
     (dense + erf-GELU + LayerNorm 1e-12), tied decoder + cls.predictions.bias and the fused loss
-    (VocabXentFn). With no labelled row the result is 0 / 0 = NaN, as the reference's."""
+    (VocabXentFn). With no labelled row the result is 0 / 0 = NaN, as the reference's.
+    `rows`: the (src, labels) pair of labelled_rows when the caller has it already (a device batch
+    reads the row count back together with its other status); None computes it from `labels`."""
 
     @staticmethod
     def apply(lang_output, labels, ignore_index, anchor, head_store, word_store,
-              wname="embeddings.word_embeddings.weight", prefix="cls.predictions."):
+              wname="embeddings.word_embeddings.weight", prefix="cls.predictions.", rows=None):
         x = lang_output  # [rows][H] or [P][Lt][H], e.g. the text rows of the joint buffer, in place
-        src, lab = labelled_rows(labels, ignore_index, x.device)
+        src, lab = labelled_rows(labels, ignore_index, x.device) if rows is None else rows
         hc = RowsGatherFn.apply(x, src, None)
         t = LinearFn.apply(hc, anchor, head_store, prefix + "transform.dense.weight",
                            prefix + "transform.dense.bias", GELU)

@@ -34,8 +34,13 @@ visn_fc detached, and the ViT parameters receive their exact (zero) gradient wit
 Text+image stage (scripts/wikihow_pretrain.sh). Per batch ONE objective is
 drawn (:1817) from the subset of image_swapping (ISP), patch_based_image_swapping (PISP) and
 patch_based_mrm_classification (MRM) the model was built with, and the masked-LM term is added:
-  * 2 of the N steps are sub-sampled, images by index and their tokens / mask / types / labels by
-    `subsample_text` on the host (:1979-2032);
+  * the batch is masked afresh every step by `mask_tokens_sentence` (trainers/train_utils.py:
+    19-66 as the counter-based kernel mmseq_mlm_mask: ids in place, labels out, on the device);
+  * 2 of the N steps are sub-sampled, images by index and their tokens / mask / types / labels
+    (:1979-2032) where the batch lives: device tensors by `subsample_text_device`
+    (mmseq_subsample_text) followed by the labelled-row compaction (mmseq_rows_compact), with ONE
+    read-back of two integers per step (bad stories, labelled rows); host tensors by
+    `subsample_text` on the host, as before;
   * ISP (:2034-2053): rand() > 0.5 "swaps" the two images, label 0 (the reference keeps a view of
     one image while overwriting it, so a swapped story holds the first image twice), else label
     1; loss CrossEntropy(image_swapping_mlp(pooled));
@@ -138,6 +143,71 @@ def subsample_text(input_ids, attention_mask, token_type_ids, masked_lm_labels, 
 
     return (take(ids, pad_id), take(attention_mask, 0), take(token_type_ids, 0),
             take(masked_lm_labels, ignore_index))
+
+
+def subsample_text_device(input_ids, attention_mask, token_type_ids, masked_lm_labels, sub_idx,
+                          n_steps, cls_id, pad_id, ignore_index, device="cuda", status=None):
+    """`subsample_text` on the device (mmseq_subsample_text): the same arguments and returns, the
+    tensors on the device (that of input_ids when it is a device tensor, else host tensors are
+    copied to `device` first). Raises ValueError naming the number of stories for which the host
+    function raises. With `status` (int32 [>= 1] on the device, zeroed by the caller) the bad-story
+    count is added to status[0] and NOT read back here: the caller reads it with whatever else the
+    step needs, and raises."""
+    ids = torch.as_tensor(input_ids)
+    dev = ids.device if ids.is_cuda else torch.device(device)
+
+    def on(t):
+        if t is None:
+            return None
+        return torch.as_tensor(t).to(dev, torch.int64, non_blocking=True).contiguous()
+
+    ids, mask, tt, lab = on(ids), on(attention_mask), on(token_type_ids), on(masked_lm_labels)
+    sub = on(np.asarray(sub_idx, np.int64) if not torch.is_tensor(sub_idx) else sub_idx)
+    B, L = ids.shape
+    pad = L // n_steps * sub.shape[1]
+    out = [None if t is None else torch.empty(B, pad, dtype=torch.int64, device=dev)
+           for t in (ids, mask, tt, lab)]
+    own = status is None
+    if own:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    N.subsample_text(ids, mask, tt, lab, sub, n_steps, int(cls_id), int(pad_id), int(ignore_index),
+                     out[0], out[1], out[2], out[3], status)
+    if own:
+        _raise_bad_stories(int(status.item()))
+    return tuple(out)
+
+
+def _raise_bad_stories(bad):
+    if bad:
+        raise ValueError(f"{bad} stor{'y' if bad == 1 else 'ies'} whose sub-sampled steps lack a "
+                         "cls token or exceed the padded length (lxrt/modeling.py:1986-2032)")
+
+
+_MASK_CALLS = [0]  # process-wide: mask_tokens_sentence(seed=None) never repeats a key
+
+
+def mask_tokens_sentence(inputs, tokenizer, args, seed=None, device="cuda"):
+    """Drop-in for trainers/train_utils.py:19-66 on the device (kernels.mlm_mask): 80 % [MASK],
+    10 % random word, 10 % unchanged over the tokens selected with args.mlm_probability; reads
+    tokenizer.pad_token / mask_token (convert_tokens_to_ids), len(tokenizer), args.cls_id and
+    args.mlm_ignore_index. `inputs`: int64 [B][L]; a device tensor is masked IN PLACE, a host one
+    is copied to `device` first. Returns (inputs, labels), both on the device. seed=None draws a
+    fresh key from a process-wide counter (successive calls differ); an explicit seed reproduces
+    the bits."""
+    pad_id = tokenizer.convert_tokens_to_ids(tokenizer.pad_token)
+    mask_id = tokenizer.convert_tokens_to_ids(tokenizer.mask_token)
+    t = torch.as_tensor(inputs)
+    if not t.is_cuda:
+        t = t.to(device, torch.int64).contiguous()
+    if t.dtype != torch.int64 or t.dim() != 2 or not t.is_contiguous():
+        raise ValueError("mask_tokens_sentence: inputs must be contiguous int64 [B][L]")
+    stream_id = 0
+    if seed is None:
+        _MASK_CALLS[0] += 1
+        seed, stream_id = _MASK_CALLS[0], 1  # stream 1: apart from every explicit seed's stream 0
+    labels = K.mlm_mask(t, pad_id, args.cls_id, mask_id, len(tokenizer), args.mlm_ignore_index,
+                        args.mlm_probability, seed, stream_id)
+    return t, labels
 
 
 class LXRTPretraining(nn.Module):
@@ -426,10 +496,20 @@ class LXRTPretraining(nn.Module):
     def _forward_mm(self, input_ids, token_type_ids, attention_mask, masked_lm_labels, images,
                     draws):
         """:1734-2484 for the text+image stage: one objective per batch + the masked-LM term.
-        Returns (total_loss, [[objective_loss, mlm_loss]], answer_score)."""
+        Returns (total_loss, [[objective_loss, mlm_loss]], answer_score). A device `input_ids`
+        takes the device input path (attention_mask, token_type_ids and masked_lm_labels must then
+        be on that device); host tensors go through the host sub-sampling."""
         if masked_lm_labels is None or images is None:
-            raise ValueError("the text+image stage needs masked_lm_labels and images")
+            raise ValueError("the text+image stage needs masked_lm_labels and images: "
+                             "pretraining.mask_tokens_sentence(input_ids, tokenizer, args) masks a "
+                             "batch on the device and returns the labels")
         dev = self.device_
+        on_device = torch.is_tensor(input_ids) and input_ids.is_cuda
+        if on_device:
+            for name, t in (("attention_mask", attention_mask), ("token_type_ids", token_type_ids),
+                            ("masked_lm_labels", masked_lm_labels)):
+                if t is not None and not (torch.is_tensor(t) and t.device == input_ids.device):
+                    raise ValueError(f"input_ids is on {input_ids.device}: {name} must be there too")
         images = images.to(dev, torch.float32).contiguous()
         B, Nimg = images.shape[:2]
         inner = self.bert
@@ -448,10 +528,23 @@ class LXRTPretraining(nn.Module):
         sub_idx = np.asarray(draws["sub_idx"], np.int64)
         if attention_mask is None:
             attention_mask = torch.ones_like(torch.as_tensor(input_ids))
-        # sub-sampling: integer work on the host, the images are only indexed (mmseq_vit_im2col)
-        ids, mask, tt, labels = subsample_text(input_ids, attention_mask, token_type_ids,
-                                               masked_lm_labels, sub_idx, Nimg, self.cls_id,
-                                               self.pad_id, self.mlm_ignore_index)
+        # sub-sampling: integer work, the images are only indexed (mmseq_vit_im2col)
+        mlm_rows = None
+        if on_device:
+            # a device batch stays there: sub-sampling and the labelled-row compaction are two
+            # kernels whose counts (bad stories, labelled rows) come back in ONE read
+            status = torch.zeros(2, dtype=torch.int32, device=input_ids.device)
+            ids, mask, tt, labels = subsample_text_device(
+                input_ids, attention_mask, token_type_ids, masked_lm_labels, sub_idx, Nimg,
+                self.cls_id, self.pad_id, self.mlm_ignore_index, status=status)
+            src, lab = K.compact_rows(labels, self.mlm_ignore_index, status[1:])
+            bad, n_rows = status.tolist()
+            _raise_bad_stories(bad)
+            mlm_rows = (src[:n_rows], lab[:n_rows])
+        else:
+            ids, mask, tt, labels = subsample_text(input_ids, attention_mask, token_type_ids,
+                                                   masked_lm_labels, sub_idx, Nimg, self.cls_id,
+                                                   self.pad_id, self.mlm_ignore_index)
         pairs = torch.as_tensor(sub_idx).clone()
         if obj == ISP:
             # :2042-2046 keeps a VIEW of image y while overwriting it, so a "swapped" story holds
@@ -524,7 +617,8 @@ class LXRTPretraining(nn.Module):
             scores = self._lin(pooled, st, obj + "_mlp").float()
             obj_loss = torch.nn.functional.cross_entropy(scores, obj_labels.to(dev))
         self.last_objective_logits, self.last_objective_labels = scores.detach(), obj_labels
-        mlm = K.MlmLossFn.apply(lang, labels, self.mlm_ignore_index, self._anchor, st, st_in)
+        mlm = K.MlmLossFn.apply(lang, labels, self.mlm_ignore_index, self._anchor, st, st_in,
+                                rows=mlm_rows)
         total = obj_loss + mlm
         losses = torch.stack([obj_loss.detach(), mlm.detach()]).view(1, 2)
         return total, losses, answer.detach()
