@@ -537,6 +537,71 @@ mmseq_status mmseq_beam_search(int B, int N, int H, int W, const float* doc, con
                                int64_t workspace_bytes, mmseq_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Every finished hypothesis of the beam (generator.py:8-38 Beam, its `finished` list): the decode
+ * of mmseq_beam_search, same inputs, same workspace (mmseq_beam_workspace), same limits and
+ * status codes, same stream ordering; it reports what the last step (t = N-2) selected.
+ *   orders [B][W][N] int64, scores [B][W] f32, count [B] int32      outputs
+ *   entry i of story b is the i-th entry the last step selected, ascending by (score, flat
+ *   index), completed with the smallest index it does not contain. A selected entry whose
+ *   N - 1 picks hold a repeat (it took a pointed step somewhere on its way, score ~1e9: k exceeds
+ *   the unpointed count, as for N = 3 with W = 16) is no ordering and is left out; the entries
+ *   after it move up. count[b] is the number of entries reported; rows count[b] .. W-1 of
+ *   orders[b] and scores[b] are NOT written.
+ *   N = 1: count 1, order [0], score 0.
+ * Entry 0 is mmseq_beam_search's order / score for the same inputs, bit for bit (the two entry
+ * points enqueue the same kernels on the same data).
+ * ------------------------------------------------------------------------------------------ */
+mmseq_status mmseq_beam_search_nbest(int B, int N, int H, int W, const float* doc,
+                                     const float* okey, const float* hist, const float* h0,
+                                     const float* c0, const float* w_ih, const float* b_ih,
+                                     const float* w_hh, const float* b_hh, const float* w_q,
+                                     const float* b_q, const float* w_pw, const float* w_t,
+                                     const float* b_t, int64_t* orders, float* scores,
+                                     int32_t* count, void* workspace, int64_t workspace_bytes,
+                                     mmseq_stream stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Teacher-forced pointer scores of K candidate orders per story (modeling_bert.py:943-1174, the
+ * pointer loop of BertForOrdering._forward run with labels = a candidate, after ONE encode):
+ * candidate k of story b is a beam slot that never branches. At step t = 0 .. N-2 it runs exactly
+ * the step of mmseq_beam_search above (x = doc[last] or 0, LSTM cell, q, keys from the four
+ * projected blocks of hist, e with -1e9 where pointed, log-softmax; the same kernels) and,
+ * instead of selecting, adds -logp[orders[k][t]] to its score:
+ *   nll[b][k] = sum_{t < N-1} -logp_t[orders[k][t]]        step_nll[b][k][t] = the t-th term
+ * summed in step order. Only the first N - 1 entries of a candidate are read; the last one is
+ * implied. N = 1 gives nll 0 and writes no step_nll. A candidate scored here and the same order
+ * found by mmseq_beam_search agree to fp32 GEMM rounding (the dense parts run at B*K rows here
+ * and at B*W rows there), not bit for bit.
+ *   doc .. b_t   as mmseq_beam_search
+ *   orders       int64; candidate k of story b starts at orders + b * story_stride + k * N.
+ *                story_stride = 0: one list [K][N] shared by all stories; K * N: [B][K][N]
+ *   nll          [B][K] f32;  step_nll [B][K][N-1] f32 or NULL
+ * Invalid candidates: one whose first N - 1 entries hold a value outside [0, N) or a repeat gets
+ * nll = +INFINITY and a step_nll row of +INFINITY. Its entries are checked before any of them
+ * forms an address (the slot then runs on the order 0, 1, .., N-2 and its result is discarded), so
+ * no value in `orders` can cause an out-of-range access, and the other candidates of the call
+ * are unaffected bit for bit.
+ * Supported: 1 <= N <= 16, K >= 1, B * K * 4H < 2^31, B and H within mmseq_beam_search's limits;
+ * anything else returns MMSEQ_EUNSUPPORTED before anything is launched, a null buffer (step_nll
+ * excepted), a story_stride that is neither 0 nor >= K * N, or a short / unaligned workspace
+ * MMSEQ_EINVAL.
+ *   workspace: mmseq_order_score_workspace(B, N, H, K) bytes (0 for an unsupported shape), 16-byte
+ *     aligned, contents irrelevant on entry (every element that is read was written by this call
+ *     first; NaN in it reaches no output). Nothing is written outside nll, step_nll and the
+ *     workspace. Two calls on the same inputs give bit-identical outputs; no atomics.
+ * Stream ordering as for mmseq_beam_search.
+ * ------------------------------------------------------------------------------------------ */
+int64_t mmseq_order_score_workspace(int B, int N, int H, int K);
+mmseq_status mmseq_order_score(int B, int N, int H, int K, const float* doc, const float* okey,
+                               const float* hist, const float* h0, const float* c0,
+                               const float* w_ih, const float* b_ih, const float* w_hh,
+                               const float* b_hh, const float* w_q, const float* b_q,
+                               const float* w_pw, const float* w_t, const float* b_t,
+                               const int64_t* orders, int64_t story_stride, float* nll,
+                               float* step_nll, void* workspace, int64_t workspace_bytes,
+                               mmseq_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * MX-fp8 forward GEMMs (BASELINE config 5 "fp8 MFMA"; v_mfma_scale_f32_16x16x128_f8f6f4).
  *  Format: OCP e4m3 elements, one E8M0 scale (2^(s-127)) per 32 consecutive K-elements of a row
  *  (OCP MX: s = floor(log2 amax) - 8 + 127, elements = x / 2^(s-127) clamped to +-448, RNE).

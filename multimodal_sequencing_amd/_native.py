@@ -156,6 +156,10 @@ _SIGS = {
     "mmseq_lstm_cell_bwd": (ctypes.c_int, [ctypes.c_int] * 2 + [_vp] * 8),
     "mmseq_beam_workspace": (ctypes.c_int64, [ctypes.c_int] * 4),
     "mmseq_beam_search": (ctypes.c_int, [ctypes.c_int] * 4 + [_vp] * 17 + [_c_i64, _vp]),
+    "mmseq_beam_search_nbest": (ctypes.c_int, [ctypes.c_int] * 4 + [_vp] * 18 + [_c_i64, _vp]),
+    "mmseq_order_score_workspace": (ctypes.c_int64, [ctypes.c_int] * 4),
+    "mmseq_order_score": (ctypes.c_int, [ctypes.c_int] * 4 + [_vp] * 15 + [_c_i64] +
+                          [_vp] * 3 + [_c_i64, _vp]),
     "mmseq_mxfp8_scale_bytes": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int]),
     "mmseq_quant_mxfp8": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _c_i64, ctypes.c_int,
                                          _vp, _c_i64, _vp, _vp]),
@@ -641,6 +645,35 @@ def beam_workspace(B, N, H, W):
     return int(lib().mmseq_beam_workspace(B, N, H, W))
 
 
+def _beam_inputs(what, doc, okey, hist, h0, c0, weights, extra):
+    """The checks the decoder entries share -> the 14 input pointers in ABI order. `extra`:
+    ((tensor, dtype, shape), ...) outputs / index tensors that must be contiguous too."""
+    B, N, H = doc.shape
+    w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t = weights
+    shapes = ((doc, (B, N, H)), (okey, (B, N, H)), (hist, (B, N, N, H + 2)), (h0, (B, H)),
+              (c0, (B, H)), (w_ih, (4 * H, H)), (b_ih, (4 * H,)), (w_hh, (4 * H, H)),
+              (b_hh, (4 * H,)), (w_q, (H, H)), (b_q, (H,)), (w_pw, (H, 4 * (H + 2))))
+    _dev(*(t for t, _ in shapes), w_t, b_t, *(t for t, _, _ in extra))
+    for t, shp in shapes:
+        if t.dtype != torch.float32 or tuple(t.shape) != shp or not t.is_contiguous():
+            raise ValueError(f"{what}: contiguous f32 {shp} expected, got {tuple(t.shape)} "
+                             f"{t.dtype}")
+    for t, n in ((w_t, H), (b_t, 1)):
+        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"{what}: tanh_linear weight [H] / bias [1] f32 expected")
+    for t, dt, shp in extra:
+        if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous():
+            raise ValueError(f"{what}: contiguous {dt} {shp} expected, got {tuple(t.shape)} "
+                             f"{t.dtype}")
+    return [_p(t) for t in (doc, okey, hist, h0, c0, w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t,
+                            b_t)]
+
+
+def _ws_bytes(workspace):
+    _dev(workspace)
+    return workspace.numel() * workspace.element_size()
+
+
 def beam_search(doc, okey, hist, h0, c0, weights, W, order, score, workspace):
     """mmseq_beam_search: doc / okey [B][N][H], hist [B][N][N][H+2], h0 / c0 [B][H] (f32,
     contiguous); weights = (w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t) in the head store's
@@ -648,26 +681,57 @@ def beam_search(doc, okey, hist, h0, c0, weights, W, order, score, workspace):
     of at least beam_workspace(B, N, H, W) bytes. Returns the status for MMSEQ_EUNSUPPORTED (the
     caller decides what to do instead) and raises on every other failure."""
     B, N, H = doc.shape
-    w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t = weights
-    shapes = ((doc, (B, N, H)), (okey, (B, N, H)), (hist, (B, N, N, H + 2)), (h0, (B, H)),
-              (c0, (B, H)), (w_ih, (4 * H, H)), (b_ih, (4 * H,)), (w_hh, (4 * H, H)),
-              (b_hh, (4 * H,)), (w_q, (H, H)), (b_q, (H,)), (w_pw, (H, 4 * (H + 2))), (score, (B,)))
-    _dev(order, workspace, *(t for t, _ in shapes), w_t, b_t)
-    for t, shp in shapes:
-        if t.dtype != torch.float32 or tuple(t.shape) != shp or not t.is_contiguous():
-            raise ValueError(f"beam_search: contiguous f32 {shp} expected, got {tuple(t.shape)} "
-                             f"{t.dtype}")
-    for t, n in ((w_t, H), (b_t, 1)):
-        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
-            raise ValueError("beam_search: tanh_linear weight [H] / bias [1] f32 expected")
     if order.dtype != torch.int64 or tuple(order.shape) != (B, N) or not order.is_contiguous():
         raise ValueError("beam_search: order must be contiguous int64 [B][N]")
-    st = lib().mmseq_beam_search(B, N, H, int(W), _p(doc), _p(okey), _p(hist), _p(h0), _p(c0),
-                                 _p(w_ih), _p(b_ih), _p(w_hh), _p(b_hh), _p(w_q), _p(b_q),
-                                 _p(w_pw), _p(w_t), _p(b_t), _p(order), _p(score), _p(workspace),
-                                 workspace.numel() * workspace.element_size(), _stream())
+    ptrs = _beam_inputs("beam_search", doc, okey, hist, h0, c0, weights,
+                        ((order, torch.int64, (B, N)), (score, torch.float32, (B,))))
+    st = lib().mmseq_beam_search(B, N, H, int(W), *ptrs, _p(order), _p(score), _p(workspace),
+                                 _ws_bytes(workspace), _stream())
     if st != EUNSUPPORTED:
         _check(st, "mmseq_beam_search")
+    return st
+
+
+def beam_search_nbest(doc, okey, hist, h0, c0, weights, W, orders, scores, count, workspace):
+    """mmseq_beam_search_nbest: the inputs and workspace of beam_search; orders int64 [B][W][N],
+    scores f32 [B][W], count int32 [B]. Rows count[b] .. W-1 are not written. Returns the status
+    for MMSEQ_EUNSUPPORTED and raises on every other failure."""
+    B, N, H = doc.shape
+    W = int(W)
+    ptrs = _beam_inputs("beam_search_nbest", doc, okey, hist, h0, c0, weights,
+                        ((orders, torch.int64, (B, W, N)), (scores, torch.float32, (B, W)),
+                         (count, torch.int32, (B,))))
+    st = lib().mmseq_beam_search_nbest(B, N, H, W, *ptrs, _p(orders), _p(scores), _p(count),
+                                       _p(workspace), _ws_bytes(workspace), _stream())
+    if st != EUNSUPPORTED:
+        _check(st, "mmseq_beam_search_nbest")
+    return st
+
+
+def order_score_workspace(B, N, H, K):
+    """Bytes of workspace mmseq_order_score needs; 0 where the shape is unsupported."""
+    return int(lib().mmseq_order_score_workspace(B, N, H, K))
+
+
+def order_score(doc, okey, hist, h0, c0, weights, orders, nll, step_nll, workspace):
+    """mmseq_order_score: the inputs of beam_search; orders int64 [K][N] (one list shared by all
+    stories) or [B][K][N]; nll f32 [B][K]; step_nll f32 [B][K][N-1] or None; workspace of at
+    least order_score_workspace(B, N, H, K) bytes. Returns the status for MMSEQ_EUNSUPPORTED and
+    raises on every other failure."""
+    B, N, H = doc.shape
+    if orders.dim() not in (2, 3):
+        raise ValueError("order_score: orders must be int64 [K][N] or [B][K][N]")
+    K = int(orders.shape[-2])
+    oshape = (K, N) if orders.dim() == 2 else (B, K, N)
+    extra = [(orders, torch.int64, oshape), (nll, torch.float32, (B, K))]
+    if step_nll is not None:
+        extra.append((step_nll, torch.float32, (B, K, N - 1)))
+    ptrs = _beam_inputs("order_score", doc, okey, hist, h0, c0, weights, extra)
+    st = lib().mmseq_order_score(B, N, H, K, *ptrs, _p(orders), 0 if orders.dim() == 2 else K * N,
+                                 _p(nll), _p(step_nll) if step_nll is not None else None,
+                                 _p(workspace), _ws_bytes(workspace), _stream())
+    if st != EUNSUPPORTED:
+        _check(st, "mmseq_order_score")
     return st
 
 

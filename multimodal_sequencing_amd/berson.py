@@ -461,13 +461,244 @@ def berson_pointer_network(args, model, tokenizer, inputs):
     return beam_search_pointer(args, model, **berson)
 
 
-def berson_pointer_network_batch(args, model, tokenizer, inputs):
-    """Ordering indices for the B >= 1 stories of `inputs` (same keys as berson_pointer_network)
-    -> list of B lists."""
+
+
+def _batch_inputs(model, inputs):
     berson = prepare_berson_inputs(inputs["input_ids"], inputs["labels"], model.n_steps,
                                    device=model.device_)
     images = inputs.get("images")
     if images is not None:
         images = images.to(model.device_, torch.float32).contiguous()
     berson["images"] = images
-    return beam_search_pointer_batch(args, model, **berson)
+    return berson
+
+
+def berson_pointer_network_batch(args, model, tokenizer, inputs, decode="beam"):
+    """Ordering indices for the B >= 1 stories of `inputs` (same keys as berson_pointer_network)
+    -> list of B lists. decode="beam": the device-resident beam search. decode="exact": the
+    arg-min over all N! orders (exact_order_batch, N <= 7); `model.last_beam_scores` then holds
+    the exact optimum's scores."""
+    if decode not in ("beam", "exact"):
+        raise ValueError(f"decode must be 'beam' or 'exact', got {decode!r}")
+    berson = _batch_inputs(model, inputs)
+    if decode == "beam":
+        return beam_search_pointer_batch(args, model, **berson)
+    with torch.no_grad():
+        enc = model.encode(**berson)
+        order, model.last_beam_scores, _ = exact_order_batch(args, model, enc)
+    return order.tolist()
+
+
+# ------------------------------------------------------------------------------------------------
+# Scoring candidate orders, n-best and exact decode on ONE encoder output.
+SCORE_WS_CAP = 256 << 20  # bytes of mmseq_order_score workspace per call; above it K is chunked
+EXACT_MAX_N = 7           # 7! = 5040 candidates per story
+
+
+def check_orders(orders, B, N):
+    """Host-side validation of candidate orders given as a list or a CPU tensor -> int64 CPU tensor
+    [K][N] or [B][K][N]. Every candidate must be a permutation of 0 .. N-1; a ValueError names
+    the first one that is not."""
+    try:
+        o = torch.as_tensor(orders)
+    except (ValueError, TypeError) as e:  # ragged lists
+        raise ValueError(f"orders: every candidate must hold N = {N} entries ({e})") from None
+    if o.dtype.is_floating_point or o.dtype == torch.bool:
+        raise ValueError(f"orders must hold integers, got {o.dtype}")
+    o = o.to(torch.int64)
+    if o.dim() not in (2, 3) or o.shape[-1] != N or o.shape[-2] < 1:
+        raise ValueError(f"orders must be [K][{N}] or [{B}][K][{N}] with K >= 1, got "
+                         f"{tuple(o.shape)}")
+    if o.dim() == 3 and o.shape[0] != B:
+        raise ValueError(f"orders [B][K][N] must hold B = {B} stories, got {o.shape[0]}")
+    flat = o.reshape(-1, N)
+    ok = (flat.sort(-1).values == torch.arange(N)).all(-1)
+    if not bool(ok.all()):
+        i = int((~ok).nonzero()[0])
+        K = o.shape[-2]
+        where = f"candidate {i % K}" + (f" of story {i // K}" if o.dim() == 3 else "")
+        row = flat[i].tolist()
+        why = "an entry outside 0 .. N-1" if min(row) < 0 or max(row) >= N else "a repeated entry"
+        raise ValueError(f"orders: {where} = {row} is no permutation of 0 .. {N - 1}: {why}")
+    return o.contiguous()
+
+
+@torch.no_grad()
+def score_orders_host(args, model, enc, orders, return_steps=False, chunk=128):
+    """Teacher-forced pointer NLL of candidate orders in torch, built on `model.step` (the
+    per-story decoder's step, :1368-1402): the second scorer beside mmseq_order_score and what
+    score_orders_batch falls back to where the ABI reports the shape unsupported. `orders` as for
+    score_orders_batch (a device tensor is copied to the host and validated) -> nll f32 [B][K]
+    (and the per-step terms [B][K][N-1]) on the encoder output's device."""
+    (sent, _p, dec_init, okeys, _cls, cls_mat, _cs, cs_mat, _h1, _h2) = enc
+    B, N, H = sent.shape
+    dev = sent.device
+    o = check_orders(orders.cpu() if torch.is_tensor(orders) else orders, B, N).to(dev)
+    Kn = o.shape[-2]
+    nll = torch.zeros(B, Kn, dtype=torch.float32, device=dev)
+    steps = torch.zeros(B, Kn, max(N - 1, 0), dtype=torch.float32, device=dev)
+    for b in range(B if N > 1 else 0):
+        hist1 = torch.cat([cls_mat[b:b + 1], torch.softmax(cs_mat[b:b + 1], -1)], -1)
+        for k0 in range(0, Kn, chunk):
+            cand = (o if o.dim() == 2 else o[b])[k0:k0 + chunk]
+            k = cand.shape[0]
+            ar = torch.arange(k, device=dev)
+            hist = hist1.expand(k, -1, -1, -1).contiguous()
+            rela = hist.clone()
+            h = dec_init[0][0][b:b + 1].expand(k, -1).contiguous()
+            c = dec_init[1][0][b:b + 1].expand(k, -1).contiguous()
+            rela_mask = (1 - torch.eye(N, dtype=torch.int64, device=dev))[None].repeat(k, 1, 1)
+            pointed = torch.zeros(k, N, dtype=torch.int64, device=dev)
+            x = torch.zeros(k, H, dtype=sent.dtype, device=dev)
+            total = torch.zeros(k, dtype=torch.float32, device=dev)
+            for t in range(N - 1):
+                l1_idx = l2_idx = None
+                if t > 0:
+                    l1_idx = cand[:, t - 1]
+                    x = sent[b][l1_idx]
+                    pointed[ar, l1_idx] = 1
+                    rela_mask[ar, :, l1_idx] = 0
+                    rela_mask[ar, l1_idx] = 0
+                    if t > 1:
+                        l2_idx = cand[:, t - 2]
+                h, c, logp, rela = model.step(x, h, c, okeys[b:b + 1], pointed, rela, rela_mask,
+                                              hist, l1_idx, l2_idx)
+                step = -logp.float().gather(1, cand[:, t:t + 1])[:, 0]
+                steps[b, k0:k0 + k, t] = step
+                total = total + step
+            nll[b, k0:k0 + k] = total
+    return (nll, steps) if return_steps else nll
+
+
+def _score_chunk(B, N, H, Kn):
+    """-> (candidates per call, workspace bytes): the largest count, halving from Kn, whose
+    workspace fits SCORE_WS_CAP (a single candidate is always tried); bytes 0 = unsupported."""
+    kc = Kn
+    while kc > 1:
+        nbytes = N_.order_score_workspace(B, N, H, kc)
+        if 0 < nbytes <= SCORE_WS_CAP:
+            return kc, nbytes
+        kc = (kc + 1) // 2
+    return 1, N_.order_score_workspace(B, N, H, 1)
+
+
+@torch.no_grad()
+def score_orders_batch(args, model, enc, orders, return_steps=False):
+    """Teacher-forced pointer NLL of K candidate orders for every story of an encode() tuple
+    through mmseq_order_score: what `model({**inputs, "labels": order})` reports as the pointer
+    loss x (N - 1), without the encoder. `orders`: a list or tensor [K][N] (one list for all
+    stories) or [B][K][N]. A list or CPU tensor is validated here (ValueError naming the
+    candidate); a device tensor is not synchronised on, and a candidate in it that is no
+    permutation comes back as +inf. -> nll f32 [B][K] on the device, with return_steps=True also
+    the per-step terms [B][K][N-1].
+
+    The workspace is cached on the model like the beam's. Its size grows with B*K*H, so K is
+    split (halved until it fits) into chunks whose workspace stays within SCORE_WS_CAP = 256 MiB
+    per call (B = 32, H = 768, all 120 orders of N = 5 need 90 MiB: one call; the 5040 orders of
+    N = 7 at H = 1024 go in chunks of 158). Where the ABI reports the shape
+    unsupported (N > 16) the candidates go through score_orders_host."""
+    (sent, _p, dec_init, okeys, _cls, cls_mat, _cs, cs_mat, _h1, _h2) = enc
+    B, N, H = sent.shape
+    dev = sent.device
+    if torch.is_tensor(orders) and orders.is_cuda:
+        o = orders
+        if o.dtype != torch.int64 or o.dim() not in (2, 3) or o.shape[-1] != N or \
+                o.shape[-2] < 1 or (o.dim() == 3 and o.shape[0] != B):
+            raise ValueError(f"orders must be int64 [K][{N}] or [{B}][K][{N}] with K >= 1, got "
+                             f"{o.dtype} {tuple(o.shape)}")
+    else:
+        o = check_orders(orders, B, N).to(dev)
+    Kn = int(o.shape[-2])
+    kc, nbytes = _score_chunk(B, N, H, Kn)
+    if nbytes == 0:
+        return score_orders_host(args, model, enc, o, return_steps)
+    nll = torch.empty(B, Kn, dtype=torch.float32, device=dev)
+    steps = torch.empty(B, Kn, N - 1, dtype=torch.float32, device=dev) if return_steps else None
+    hist = torch.cat([cls_mat, torch.softmax(cs_mat, -1)], -1).contiguous()
+    ins = (sent.contiguous(), okeys.contiguous(), hist, dec_init[0][0].contiguous(),
+           dec_init[1][0].contiguous(), [model.store.f32(n) for n in _BEAM_WEIGHTS])
+    cache = model.__dict__.setdefault("_score_ws", {})
+    for k0 in range(0, Kn, kc):
+        k = min(kc, Kn - k0)
+        nb = nbytes if k == kc else N_.order_score_workspace(B, N, H, k)
+        ws = cache.get((B, N, H, k))
+        if ws is None:
+            ws = cache[(B, N, H, k)] = torch.empty(nb // 4, dtype=torch.float32, device=dev)
+        whole = k == Kn
+        o_c = o if whole else o[..., k0:k0 + k, :].contiguous()
+        nll_c = nll if whole else torch.empty(B, k, dtype=torch.float32, device=dev)
+        st_c = None
+        if return_steps:
+            st_c = steps if whole else torch.empty(B, k, N - 1, dtype=torch.float32, device=dev)
+        N_._check_shape(N_.order_score(*ins, o_c.contiguous(), nll_c, st_c, ws),
+                        "mmseq_order_score")
+        if not whole:
+            nll[:, k0:k0 + k] = nll_c
+            if return_steps:
+                steps[:, k0:k0 + k] = st_c
+    return (nll, steps) if return_steps else nll
+
+
+def berson_score_orders(args, model, tokenizer, inputs, orders, return_steps=False):
+    """Pointer NLL of candidate orders for the B >= 1 stories of `inputs` (same keys as
+    berson_pointer_network_batch): one encode, one scoring call -> score_orders_batch's result."""
+    with torch.no_grad():
+        enc = model.encode(**_batch_inputs(model, inputs))
+        return score_orders_batch(args, model, enc, orders, return_steps)
+
+
+def exact_from_scores(nll):
+    """nll [B][K] -> (index of the smallest score [B], that score [B], second-smallest minus
+    smallest [B]; inf where K = 1). Ties go to the LOWEST candidate index, stated here instead of
+    left to argmin's choice among equals: the smallest index whose score equals the minimum."""
+    B, Kn = nll.shape
+    best = nll.min(1).values
+    ar = torch.arange(Kn, device=nll.device)
+    idx = torch.where(nll == best[:, None], ar, torch.full_like(ar, Kn)).min(1).values
+    rest = nll.masked_fill(ar[None] == idx[:, None], float("inf"))
+    return idx, best, rest.min(1).values - best
+
+
+@torch.no_grad()
+def exact_order_batch(args, model, enc):
+    """The optimum over ALL N! orders (itertools.permutations order) for every story of an
+    encode() tuple, through one score_orders_batch -> (order int64 [B][N], score f32 [B], margin
+    f32 [B] = second-best minus best) on the device. Ties go to the lowest candidate index.
+    N <= 7; ValueError above."""
+    import itertools
+    B, N, _H = enc[0].shape
+    if N > EXACT_MAX_N:
+        raise ValueError(f"exact_order_batch enumerates N! orders: N = {N} exceeds {EXACT_MAX_N}")
+    perms = torch.tensor(list(itertools.permutations(range(N))), dtype=torch.int64,
+                         device=enc[0].device)
+    idx, best, margin = exact_from_scores(score_orders_batch(args, model, enc, perms))
+    return perms[idx], best, margin
+
+
+@torch.no_grad()
+def beam_nbest_batch(args, model, enc):
+    """Every finished hypothesis of the beam (mmseq_beam_search_nbest) for every story of an
+    encode() tuple -> (orders int64 [B][W][N], scores f32 [B][W], count int32 [B]) on the device,
+    ascending by score; entry 0 is beam_decode_batch's result. Rows count[b] .. W-1 hold -1 and
+    +inf. W = args.beam_size. An unsupported shape raises (_native.Unsupported)."""
+    (sent, _p, dec_init, okeys, _cls, cls_mat, _cs, cs_mat, _h1, _h2) = enc
+    B, N, H = sent.shape
+    W = int(getattr(args, "beam_size", 16))
+    dev = sent.device
+    orders = torch.full((B, W, N), -1, dtype=torch.int64, device=dev)
+    scores = torch.full((B, W), float("inf"), dtype=torch.float32, device=dev)
+    count = torch.zeros(B, dtype=torch.int32, device=dev)
+    nbytes = N_.beam_workspace(B, N, H, W)
+    if nbytes == 0:
+        raise N_.Unsupported(f"beam_nbest_batch: B={B} N={N} H={H} W={W} is outside "
+                             "mmseq_beam_search's limits")
+    cache = model.__dict__.setdefault("_beam_ws", {})
+    ws = cache.get((B, N, H, W))
+    if ws is None:
+        ws = cache[(B, N, H, W)] = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    hist = torch.cat([cls_mat, torch.softmax(cs_mat, -1)], -1).contiguous()
+    N_._check_shape(N_.beam_search_nbest(sent.contiguous(), okeys.contiguous(), hist,
+                                         dec_init[0][0].contiguous(), dec_init[1][0].contiguous(),
+                                         [model.store.f32(n) for n in _BEAM_WEIGHTS], W, orders,
+                                         scores, count, ws), "mmseq_beam_search_nbest")
+    return orders, scores, count

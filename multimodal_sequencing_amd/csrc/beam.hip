@@ -14,6 +14,11 @@
 //   keys[j] = PROJ[0][l1][j] + PROJ[1][l2][j] + (sum_{j'} m PROJ[2][j][j']) / N
 //                                             + (sum_{i}  m PROJ[3][i][j]) / N
 // with m = (i != j, neither pointed). Likewise x W_ih^T + b_ih for x = doc[b][i] is one GEMM.
+//
+// Two more entries run the same setup and the same step (beam_story_setup, beam_step):
+// mmseq_beam_search_nbest reports every finished hypothesis of the last selection, and
+// mmseq_order_score runs K candidate orders per story as slots that never branch (W = nb = K,
+// every slot entered with score 0) and, instead of selecting, adds each slot's own pick to its nll.
 #include "common.h"
 
 namespace {
@@ -44,6 +49,35 @@ BeamWs beam_layout(int B, int N, int H, int W) {
   return w;
 }
 
+struct ScoreWs {  // mmseq_order_score: B stories x K slots that never branch, R = B*K rows
+  int64_t gx, proj, h, c, gh, q, s, zero, seq, bad, total;
+};
+
+ScoreWs score_layout(int B, int N, int H, int K) {
+  ScoreWs w;
+  const int64_t R = (int64_t)B * K;
+  int64_t o = 0;
+  w.gx = o; o += up4((int64_t)B * N * 4 * H);
+  w.proj = o; o += 4 * up4((int64_t)B * N * N * H);
+  w.h = o; o += up4(R * H);
+  w.c = o; o += up4(R * H);
+  w.gh = o; o += up4(R * 4 * H);
+  w.q = o; o += up4(R * H);
+  w.s = o; o += up4(R * N);
+  w.zero = o; o += up4(R);                // the score every slot enters a step with: 0
+  w.seq = o; o += up4(R * BEAM_MAXN);     // int32 picks, written once by the init kernel
+  w.bad = o; o += up4(R);                 // int32, 1 = invalid candidate
+  w.total = o;
+  return w;
+}
+
+// The optional n-best outputs of mmseq_beam_search_nbest (all NULL in mmseq_beam_search).
+struct NBest {
+  int64_t* orders;  // [B][W][N]
+  float* scores;    // [B][W]
+  int* count;       // [B]
+};
+
 // slot 0 of every story <- (h0, c0), score 0; N == 1: the order is [0]
 __global__ __launch_bounds__(256) void beam_init_kernel(int N, int H, int W,
                                                         const float* __restrict__ h0,
@@ -51,10 +85,17 @@ __global__ __launch_bounds__(256) void beam_init_kernel(int N, int H, int W,
                                                         float* __restrict__ h, float* __restrict__ c,
                                                         float* __restrict__ score,
                                                         int64_t* __restrict__ order,
-                                                        float* __restrict__ best) {
+                                                        float* __restrict__ best, NBest nbest) {
   const int b = blockIdx.x;
   if (N == 1) {
-    if (threadIdx.x == 0) { order[b] = 0; best[b] = 0.f; }
+    if (threadIdx.x == 0) {
+      if (order) { order[b] = 0; best[b] = 0.f; }
+      if (nbest.orders) {
+        nbest.orders[(int64_t)b * W] = 0;
+        nbest.scores[(int64_t)b * W] = 0.f;
+        nbest.count[b] = 1;
+      }
+    }
     return;
   }
   const int64_t slot = (int64_t)b * W;
@@ -156,7 +197,8 @@ __global__ __launch_bounds__(256) void beam_score_kernel(int N, int H, int W, in
 // One workgroup per story: the k smallest of the nb*N flat scores by (score, flat index) through
 // a rank count in LDS (no sort, no dynamically indexed registers), the chosen entries become
 // slots 0..k-1 of the next step in selection order with their parents' h', c'. In the last step
-// the first selected entry is the story's best hypothesis.
+// the first selected entry is the story's best hypothesis (order / best, when asked for) and the
+// selected entries that are permutations are the n-best list (nbest, when asked for).
 __global__ __launch_bounds__(256) void beam_select_kernel(int N, int H, int W, int t, int nb, int k,
                                                           int last, const float* __restrict__ s,
                                                           const int* __restrict__ seq_cur,
@@ -167,7 +209,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(int N, int H, int W, i
                                                           float* __restrict__ h_nxt,
                                                           float* __restrict__ c_nxt,
                                                           int64_t* __restrict__ order,
-                                                          float* __restrict__ best) {
+                                                          float* __restrict__ best, NBest nbest) {
   __shared__ float sh_s[BEAM_MAXW * BEAM_MAXN];
   __shared__ int sh_sel[BEAM_MAXW];
   __shared__ int sh_par[BEAM_MAXW];
@@ -188,18 +230,45 @@ __global__ __launch_bounds__(256) void beam_select_kernel(int N, int H, int W, i
   __syncthreads();
   if (last) {
     if (threadIdx.x == 0) {
-      const int i = sh_sel[0], w = i / N, j = i % N;
-      unsigned have = 1u << j;
-      for (int p = 0; p < t; ++p) {
-        const int v = seq_cur[(slot0 + w) * BEAM_MAXN + p];
-        order[(int64_t)b * N + p] = v;
-        have |= 1u << v;
+      if (order) {
+        const int i = sh_sel[0], w = i / N, j = i % N;
+        unsigned have = 1u << j;
+        for (int p = 0; p < t; ++p) {
+          const int v = seq_cur[(slot0 + w) * BEAM_MAXN + p];
+          order[(int64_t)b * N + p] = v;
+          have |= 1u << v;
+        }
+        order[(int64_t)b * N + t] = j;
+        int miss = 0;
+        while ((have >> miss) & 1u) ++miss;  // length N - 1 < N entries: one index is always free
+        order[(int64_t)b * N + t + 1] = miss;
+        best[b] = sh_s[i];
       }
-      order[(int64_t)b * N + t] = j;
-      int miss = 0;
-      while ((have >> miss) & 1u) ++miss;  // length N - 1 < N entries: one index is always free
-      order[(int64_t)b * N + t + 1] = miss;
-      best[b] = sh_s[i];
+      if (nbest.orders) {
+        // every selected entry in selection order; one that picked a pointed step anywhere on
+        // its way (a repeated index, score ~1e9) is no permutation and is left out
+        int cnt = 0;
+        for (int r = 0; r < k; ++r) {
+          const int i = sh_sel[r], w = i / N, j = i % N;
+          unsigned have = 1u << j;
+          bool ok = true;
+          for (int p = 0; p < t; ++p) {
+            const unsigned bit = 1u << seq_cur[(slot0 + w) * BEAM_MAXN + p];
+            ok = ok && !(have & bit);
+            have |= bit;
+          }
+          if (!ok) continue;
+          int64_t* o = nbest.orders + ((int64_t)b * W + cnt) * N;
+          for (int p = 0; p < t; ++p) o[p] = seq_cur[(slot0 + w) * BEAM_MAXN + p];
+          o[t] = j;
+          int miss = 0;
+          while ((have >> miss) & 1u) ++miss;
+          o[t + 1] = miss;
+          nbest.scores[(int64_t)b * W + cnt] = sh_s[i];
+          ++cnt;
+        }
+        nbest.count[b] = cnt;
+      }
     }
     return;
   }
@@ -220,9 +289,166 @@ __global__ __launch_bounds__(256) void beam_select_kernel(int N, int H, int W, i
   }
 }
 
+// mmseq_order_score, one workgroup per slot (story b, candidate k): the candidate's N - 1 picks
+// are validated BEFORE any of them is used as an index; the whole seq row is written here, once
+// (an invalid candidate runs as 0, 1, .., N-2 so that every later indexed read stays in bounds,
+// and is marked bad), (h, c) <- (h0, c0), nll <- 0, or +inf with its step_nll row where bad.
+__global__ __launch_bounds__(256) void order_init_kernel(int N, int H, int K,
+                                                         const int64_t* __restrict__ orders,
+                                                         int64_t story_stride,
+                                                         const float* __restrict__ h0,
+                                                         const float* __restrict__ c0,
+                                                         float* __restrict__ h, float* __restrict__ c,
+                                                         float* __restrict__ zero,
+                                                         int* __restrict__ seq, int* __restrict__ bad,
+                                                         float* __restrict__ nll,
+                                                         float* __restrict__ step_nll) {
+  const int64_t slot = blockIdx.x;
+  const int b = (int)(slot / K), k = (int)(slot % K);
+  if (N == 1) {
+    if (threadIdx.x == 0) nll[slot] = 0.f;
+    return;
+  }
+  const int64_t* cand = orders + (int64_t)b * story_stride + (int64_t)k * N;
+  unsigned have = 0;
+  bool ok = true;
+  for (int p = 0; p < N - 1; ++p) {  // every thread: the same N - 1 loads, no LDS, no barrier
+    const int64_t v = cand[p];
+    const bool in = v >= 0 && v < N;
+    const unsigned bit = in ? 1u << (int)v : 0u;
+    ok = ok && in && !(have & bit);
+    have |= bit;
+  }
+  const int p = threadIdx.x;
+  if (p < N - 1) seq[slot * BEAM_MAXN + p] = ok ? (int)cand[p] : p;
+  if (threadIdx.x == 0) {
+    bad[slot] = ok ? 0 : 1;
+    zero[slot] = 0.f;
+    nll[slot] = ok ? 0.f : INFINITY;
+  }
+  if (!ok && step_nll && threadIdx.x < N - 1) step_nll[slot * (N - 1) + threadIdx.x] = INFINITY;
+  for (int u = threadIdx.x; u < H; u += 256) {
+    h[slot * H + u] = h0[(int64_t)b * H + u];
+    c[slot * H + u] = c0[(int64_t)b * H + u];
+  }
+}
+
+// One thread per slot after beam_score_kernel of step t (entered with score 0, so s = -logp):
+// the step's -logp of the slot's own t-th pick, added to nll in step order.
+__global__ __launch_bounds__(256) void order_pick_kernel(int64_t R, int N, int t,
+                                                         const float* __restrict__ s,
+                                                         const int* __restrict__ seq,
+                                                         const int* __restrict__ bad,
+                                                         float* __restrict__ nll,
+                                                         float* __restrict__ step_nll) {
+  const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (slot >= R || bad[slot]) return;
+  const float v = s[slot * N + seq[slot * BEAM_MAXN + t]];
+  nll[slot] += v;
+  if (step_nll) step_nll[slot * (N - 1) + t] = v;
+}
+
 inline bool beam_supported(int B, int N, int H, int W) {
   return B >= 0 && N >= 1 && N <= BEAM_MAXN && W >= 1 && W <= BEAM_MAXW && H >= 1 &&
          (int64_t)B * BEAM_MAXW * BEAM_MAXN * 4 < INT32_MAX / 2 && (int64_t)H * 4 * 4 < INT32_MAX / 2;
+}
+
+// the per-story limits of the beam, and B*K rows of 4H floats within 32-bit element counts
+inline bool score_supported(int B, int N, int H, int K) {
+  return beam_supported(B, N, H, 1) && K >= 1 && (int64_t)B * K * 4 * H < INT32_MAX &&
+         (int64_t)B * K * BEAM_MAXN < INT32_MAX;
+}
+
+struct BeamWeights {
+  const float *w_ih, *b_ih, *w_hh, *b_hh, *w_q, *b_q, *w_pw, *w_t, *b_t;
+};
+
+mmseq_status beam_gemm(int M, int Nn, int K, const float* A, int64_t lda, const float* Bm,
+                       int64_t ldb, float* C, const float* bias, mmseq_stream stream) {
+  return mmseq_gemm(0, M, Nn, K, 1, A, lda, 0, Bm, ldb, 0, C, Nn, 0, bias, MMSEQ_ACT_NONE, nullptr,
+                    nullptr, nullptr, 0, 0, 1.0f, 0, MMSEQ_F32, MMSEQ_F32, nullptr, MMSEQ_GEMM_AUTO,
+                    nullptr, 0, stream);
+}
+
+// once per call: the input gates of every sentence (GX) and the four projections of hist (PROJ)
+mmseq_status beam_story_setup(int B, int N, int H, const float* doc, const float* hist,
+                              const BeamWeights& wt, float* gx, float* proj, int64_t pstride,
+                              mmseq_stream stream) {
+  mmseq_status e;
+  if (N > 2 && (e = beam_gemm(B * N, 4 * H, H, doc, H, wt.w_ih, H, gx, wt.b_ih, stream)) != MMSEQ_OK)
+    return e;
+  for (int g = 0; g < 4; ++g)
+    if ((e = beam_gemm(B * N * N, H, H + 2, hist, H + 2, wt.w_pw + (int64_t)g * (H + 2),
+                       4 * (int64_t)(H + 2), proj + g * pstride, nullptr, stream)) != MMSEQ_OK)
+      return e;
+  return MMSEQ_OK;
+}
+
+// step t of R = B*W slots, nb of them live per story: LSTM cell in place, query, s = score - logp
+mmseq_status beam_step(int B, int N, int H, int W, int t, int nb, const BeamWeights& wt,
+                       const float* okey, const float* gx, const float* proj, int64_t pstride,
+                       const int* seq, const float* score, float* h, float* c, float* gh, float* q,
+                       float* s, mmseq_stream stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int R = B * W;
+  mmseq_status e;
+  if ((e = beam_gemm(R, 4 * H, H, h, H, wt.w_hh, H, gh, wt.b_hh, stream)) != MMSEQ_OK) return e;
+  hipLaunchKernelGGL(beam_cell_kernel, dim3(R), dim3(256), 0, st, H, W, N, t, nb, gx, wt.b_ih, gh,
+                     seq, h, c);
+  if ((e = mmseq_check_launch("beam_cell")) != MMSEQ_OK) return e;
+  if ((e = beam_gemm(R, H, H, h, H, wt.w_q, H, q, wt.b_q, stream)) != MMSEQ_OK) return e;
+  hipLaunchKernelGGL(beam_score_kernel, dim3(R), dim3(256), 0, st, N, H, W, t, nb, q, proj, pstride,
+                     okey, wt.w_t, wt.b_t, seq, score, s);
+  return mmseq_check_launch("beam_score");
+}
+
+// mmseq_beam_search (order / score) and mmseq_beam_search_nbest (nbest) are this one decode
+mmseq_status beam_run(const char* what, int B, int N, int H, int W, const float* doc,
+                      const float* okey, const float* hist, const float* h0, const float* c0,
+                      const BeamWeights& wt, int64_t* order, float* score, NBest nbest,
+                      void* workspace, int64_t workspace_bytes, mmseq_stream stream) {
+  if (!beam_supported(B, N, H, W))
+    return mmseq_set_error(MMSEQ_EUNSUPPORTED,
+                           "%s: B=%d N=%d H=%d W=%d outside 1 <= N <= %d, 1 <= W <= %d "
+                           "(or B*W*N / H too large for 32-bit row counts)",
+                           what, B, N, H, W, BEAM_MAXN, BEAM_MAXW);
+  MMSEQ_REQUIRE(doc && okey && hist && h0 && c0 && wt.w_ih && wt.b_ih && wt.w_hh && wt.b_hh &&
+                    wt.w_q && wt.b_q && wt.w_pw && wt.w_t && wt.b_t &&
+                    ((order && score) || (nbest.orders && nbest.scores && nbest.count)),
+                "%s: null buffer", what);
+  const BeamWs L = beam_layout(B, N, H, W);
+  MMSEQ_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= L.total * 4,
+                "%s: workspace must be 16-byte aligned and hold %lld bytes (got %lld)", what,
+                (long long)(L.total * 4), (long long)workspace_bytes);
+  if (B == 0) return MMSEQ_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  float* ws = reinterpret_cast<float*>(workspace);
+  float* hb[2] = {ws + L.h[0], ws + L.h[1]};
+  float* cb[2] = {ws + L.c[0], ws + L.c[1]};
+  float* sc[2] = {ws + L.score[0], ws + L.score[1]};
+  int* sq[2] = {reinterpret_cast<int*>(ws + L.seq[0]), reinterpret_cast<int*>(ws + L.seq[1])};
+  hipLaunchKernelGGL(beam_init_kernel, dim3(B), dim3(256), 0, st, N, H, W, h0, c0, hb[0], cb[0],
+                     sc[0], order, score, nbest);
+  mmseq_status e = mmseq_check_launch("beam_init");
+  if (e != MMSEQ_OK || N == 1) return e;
+  const int64_t pstride = up4((int64_t)B * N * N * H);
+  if ((e = beam_story_setup(B, N, H, doc, hist, wt, ws + L.gx, ws + L.proj, pstride, stream)) !=
+      MMSEQ_OK)
+    return e;
+  int nb = 1;
+  for (int t = 0; t < N - 1; ++t) {
+    const int cur = t & 1, nxt = cur ^ 1, last = t == N - 2;
+    const int n = nb * N, k = W < n ? W : n;
+    if ((e = beam_step(B, N, H, W, t, nb, wt, okey, ws + L.gx, ws + L.proj, pstride, sq[cur],
+                       sc[cur], hb[cur], cb[cur], ws + L.gh, ws + L.q, ws + L.s, stream)) != MMSEQ_OK)
+      return e;
+    hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(256), 0, st, N, H, W, t, nb, k, last,
+                       ws + L.s, sq[cur], sq[nxt], sc[nxt], hb[cur], cb[cur], hb[nxt], cb[nxt],
+                       order, score, nbest);
+    if ((e = mmseq_check_launch("beam_select")) != MMSEQ_OK) return e;
+    nb = k;
+  }
+  return MMSEQ_OK;
 }
 
 }  // namespace
@@ -232,6 +458,7 @@ extern "C" int64_t mmseq_beam_workspace(int B, int N, int H, int W) {
   return beam_layout(B, N, H, W).total * 4;
 }
 
+
 extern "C" mmseq_status mmseq_beam_search(int B, int N, int H, int W, const float* doc,
                                           const float* okey, const float* hist, const float* h0,
                                           const float* c0, const float* w_ih, const float* b_ih,
@@ -240,60 +467,77 @@ extern "C" mmseq_status mmseq_beam_search(int B, int N, int H, int W, const floa
                                           const float* b_t, int64_t* order, float* score,
                                           void* workspace, int64_t workspace_bytes,
                                           mmseq_stream stream) {
-  if (!beam_supported(B, N, H, W))
+  return beam_run("beam_search", B, N, H, W, doc, okey, hist, h0, c0,
+                  BeamWeights{w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t}, order, score,
+                  NBest{nullptr, nullptr, nullptr}, workspace, workspace_bytes, stream);
+}
+
+extern "C" mmseq_status mmseq_beam_search_nbest(int B, int N, int H, int W, const float* doc,
+                                                const float* okey, const float* hist,
+                                                const float* h0, const float* c0, const float* w_ih,
+                                                const float* b_ih, const float* w_hh,
+                                                const float* b_hh, const float* w_q,
+                                                const float* b_q, const float* w_pw,
+                                                const float* w_t, const float* b_t, int64_t* orders,
+                                                float* scores, int32_t* count, void* workspace,
+                                                int64_t workspace_bytes, mmseq_stream stream) {
+  return beam_run("beam_search_nbest", B, N, H, W, doc, okey, hist, h0, c0,
+                  BeamWeights{w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t}, nullptr, nullptr,
+                  NBest{orders, scores, count}, workspace, workspace_bytes, stream);
+}
+
+extern "C" int64_t mmseq_order_score_workspace(int B, int N, int H, int K) {
+  if (!score_supported(B, N, H, K)) return 0;
+  return score_layout(B, N, H, K).total * 4;
+}
+
+extern "C" mmseq_status mmseq_order_score(int B, int N, int H, int K, const float* doc,
+                                          const float* okey, const float* hist, const float* h0,
+                                          const float* c0, const float* w_ih, const float* b_ih,
+                                          const float* w_hh, const float* b_hh, const float* w_q,
+                                          const float* b_q, const float* w_pw, const float* w_t,
+                                          const float* b_t, const int64_t* orders,
+                                          int64_t story_stride, float* nll, float* step_nll,
+                                          void* workspace, int64_t workspace_bytes,
+                                          mmseq_stream stream) {
+  if (!score_supported(B, N, H, K))
     return mmseq_set_error(MMSEQ_EUNSUPPORTED,
-                           "beam_search: B=%d N=%d H=%d W=%d outside 1 <= N <= %d, 1 <= W <= %d "
-                           "(or B*W*N / H too large for 32-bit row counts)",
-                           B, N, H, W, BEAM_MAXN, BEAM_MAXW);
+                           "order_score: B=%d N=%d H=%d K=%d outside 1 <= N <= %d, 1 <= K, "
+                           "B*K*4H < 2^31 (or B / H too large for 32-bit row counts)",
+                           B, N, H, K, BEAM_MAXN);
   MMSEQ_REQUIRE(doc && okey && hist && h0 && c0 && w_ih && b_ih && w_hh && b_hh && w_q && b_q &&
-                    w_pw && w_t && b_t && order && score,
-                "beam_search: null buffer");
-  const BeamWs L = beam_layout(B, N, H, W);
+                    w_pw && w_t && b_t && orders && nll,
+                "order_score: null buffer");
+  MMSEQ_REQUIRE(story_stride == 0 || story_stride >= (int64_t)K * N,
+                "order_score: story_stride %lld is neither 0 (shared list) nor >= K*N",
+                (long long)story_stride);
+  const ScoreWs L = score_layout(B, N, H, K);
   MMSEQ_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= L.total * 4,
-                "beam_search: workspace must be 16-byte aligned and hold %lld bytes (got %lld)",
+                "order_score: workspace must be 16-byte aligned and hold %lld bytes (got %lld)",
                 (long long)(L.total * 4), (long long)workspace_bytes);
   if (B == 0) return MMSEQ_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   float* ws = reinterpret_cast<float*>(workspace);
-  const int R = B * W;
-  float* hb[2] = {ws + L.h[0], ws + L.h[1]};
-  float* cb[2] = {ws + L.c[0], ws + L.c[1]};
-  float* sc[2] = {ws + L.score[0], ws + L.score[1]};
-  int* sq[2] = {reinterpret_cast<int*>(ws + L.seq[0]), reinterpret_cast<int*>(ws + L.seq[1])};
-  hipLaunchKernelGGL(beam_init_kernel, dim3(B), dim3(256), 0, st, N, H, W, h0, c0, hb[0], cb[0],
-                     sc[0], order, score);
-  mmseq_status e = mmseq_check_launch("beam_init");
+  const int R = B * K;
+  int* seq = reinterpret_cast<int*>(ws + L.seq);
+  int* bad = reinterpret_cast<int*>(ws + L.bad);
+  hipLaunchKernelGGL(order_init_kernel, dim3(R), dim3(256), 0, st, N, H, K, orders, story_stride,
+                     h0, c0, ws + L.h, ws + L.c, ws + L.zero, seq, bad, nll, step_nll);
+  mmseq_status e = mmseq_check_launch("order_init");
   if (e != MMSEQ_OK || N == 1) return e;
-  auto gemm = [&](int M, int Nn, int K, const float* A, int64_t lda, const float* Bm, int64_t ldb,
-                  float* C, const float* bias) {
-    return mmseq_gemm(0, M, Nn, K, 1, A, lda, 0, Bm, ldb, 0, C, Nn, 0, bias, MMSEQ_ACT_NONE,
-                      nullptr, nullptr, nullptr, 0, 0, 1.0f, 0, MMSEQ_F32, MMSEQ_F32, nullptr,
-                      MMSEQ_GEMM_AUTO, nullptr, 0, stream);
-  };
-  // once per call: the input gates of every sentence and the four projections of hist
-  if (N > 2 && (e = gemm(B * N, 4 * H, H, doc, H, w_ih, H, ws + L.gx, b_ih)) != MMSEQ_OK) return e;
+  const BeamWeights wt{w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t};
   const int64_t pstride = up4((int64_t)B * N * N * H);
-  for (int g = 0; g < 4; ++g)
-    if ((e = gemm(B * N * N, H, H + 2, hist, H + 2, w_pw + (int64_t)g * (H + 2), 4 * (int64_t)(H + 2),
-                  ws + L.proj + g * pstride, nullptr)) != MMSEQ_OK)
+  if ((e = beam_story_setup(B, N, H, doc, hist, wt, ws + L.gx, ws + L.proj, pstride, stream)) !=
+      MMSEQ_OK)
+    return e;
+  for (int t = 0; t < N - 1; ++t) {  // every slot is live (nb = K) and enters with score 0
+    if ((e = beam_step(B, N, H, K, t, K, wt, okey, ws + L.gx, ws + L.proj, pstride, seq,
+                       ws + L.zero, ws + L.h, ws + L.c, ws + L.gh, ws + L.q, ws + L.s, stream)) !=
+        MMSEQ_OK)
       return e;
-  int nb = 1;
-  for (int t = 0; t < N - 1; ++t) {
-    const int cur = t & 1, nxt = cur ^ 1, last = t == N - 2;
-    const int n = nb * N, k = W < n ? W : n;
-    if ((e = gemm(R, 4 * H, H, hb[cur], H, w_hh, H, ws + L.gh, b_hh)) != MMSEQ_OK) return e;
-    hipLaunchKernelGGL(beam_cell_kernel, dim3(R), dim3(256), 0, st, H, W, N, t, nb, ws + L.gx, b_ih,
-                       ws + L.gh, sq[cur], hb[cur], cb[cur]);
-    if ((e = mmseq_check_launch("beam_cell")) != MMSEQ_OK) return e;
-    if ((e = gemm(R, H, H, hb[cur], H, w_q, H, ws + L.q, b_q)) != MMSEQ_OK) return e;
-    hipLaunchKernelGGL(beam_score_kernel, dim3(R), dim3(256), 0, st, N, H, W, t, nb, ws + L.q,
-                       ws + L.proj, pstride, okey, w_t, b_t, sq[cur], sc[cur], ws + L.s);
-    if ((e = mmseq_check_launch("beam_score")) != MMSEQ_OK) return e;
-    hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(256), 0, st, N, H, W, t, nb, k, last,
-                       ws + L.s, sq[cur], sq[nxt], sc[nxt], hb[cur], cb[cur], hb[nxt], cb[nxt],
-                       order, score);
-    if ((e = mmseq_check_launch("beam_select")) != MMSEQ_OK) return e;
-    nb = k;
+    hipLaunchKernelGGL(order_pick_kernel, dim3((R + 255) / 256), dim3(256), 0, st, (int64_t)R, N, t,
+                       ws + L.s, seq, bad, nll, step_nll);
+    if ((e = mmseq_check_launch("order_pick")) != MMSEQ_OK) return e;
   }
   return MMSEQ_OK;
 }
