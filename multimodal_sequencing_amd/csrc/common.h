@@ -86,7 +86,7 @@ __device__ __forceinline__ float act_bwd(int act, float x) {
     }
     case MMSEQ_ACT_QUICKGELU: {
       float s = 1.0f / (1.0f + __expf(-1.702f * x));
-      return s + 1.702f * x * s * (1.0f - s);
+      return s + x * (1.702f * (s * (1.0f - s)));  // s (1 - s) first: inf * 0 never forms for a finite x
     }
     case MMSEQ_ACT_TANH: {
       float t = tanhf(x);
@@ -94,9 +94,17 @@ __device__ __forceinline__ float act_bwd(int act, float x) {
     }
     case MMSEQ_ACT_GELU_TANH: {
       const float k = 0.79788456080286536f;
-      float u = k * (x + 0.044715f * x * x * x);
-      float t = tanhf(u);
-      return 0.5f * (1.0f + t) + 0.5f * x * (1.0f - t * t) * k * (1.0f + 3.0f * 0.044715f * x * x);
+      // beyond |x| = 16 exp(-2 |u|) underflows to 0: s is exactly 0 or 1 and the second term
+      // exactly 0; unclamped, x * x overflows from |x| ~ 1.8e19 and that term is 0 * inf
+      x = fminf(fmaxf(x, -16.0f), 16.0f);
+      const float u = k * (x + 0.044715f * x * x * x);
+      // 0.5 (1 + tanh u) and 1 - tanh^2 u from e = exp(-2 |u|): 1 - t * t with t = tanhf(u) cancels
+      // to a multiple of 6e-8 near |t| = 1, which the factor x k (1 + 3 c x^2) / 2 (9.4 at x = -5)
+      // made an absolute error of 5.4e-7
+      const float e = expf(-2.0f * fabsf(u));
+      const float r = 1.0f / (1.0f + e);
+      const float s = u >= 0.0f ? r : e * r;
+      return s + 0.5f * x * (4.0f * e * r * r) * k * (1.0f + 3.0f * 0.044715f * x * x);
     }
     default: return 1.0f;
   }
@@ -133,30 +141,18 @@ __device__ __forceinline__ float act_bwd_fast(int act, float x) {
   }
   if (act == MMSEQ_ACT_QUICKGELU) {
     const float s = __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * x));
-    return s + 1.702f * x * s * (1.0f - s);
+    return s + x * (1.702f * (s * (1.0f - s)));  // s (1 - s) first: inf * 0 never forms for a finite x
   }
   return act_bwd(act, x);
 }
 
-// GELU (erf form) for the bf16 GEMM epilogues without transcendentals: GELU(x) - x/2 and
-// GELU'(x) - 1/2 are odd, so both are x * P(u) with u = 2 x^2 / 25 - 1 for x clamped to [-5, 5]
-// and P a degree-12 Chebyshev fit (power basis in u). Max abs error over all x, evaluated in fp32:
-// 7.6e-6 (GELU), 2.5e-5 (GELU'); the bf16 quantum near 1 is 3.9e-3. Evaluated on element pairs so
-// the Horner chain issues as packed v_pk_fma_f32.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 gelu_poly_pair(f32x2 x, const float (&c)[13], f32x2& xc) {
-  xc = (f32x2){__builtin_amdgcn_fmed3f(x[0], -5.f, 5.f), __builtin_amdgcn_fmed3f(x[1], -5.f, 5.f)};
-  const f32x2 u = __builtin_elementwise_fma(xc * xc, (f32x2){0.08f, 0.08f}, (f32x2){-1.f, -1.f});
-  f32x2 p = (f32x2){c[12], c[12]};
-#pragma unroll
-  for (int k = 11; k >= 0; --k) p = __builtin_elementwise_fma(p, u, (f32x2){c[k], c[k]});
-  return __builtin_elementwise_fma(xc, p, (f32x2){0.5f, 0.5f});  // Phi(x) resp. GELU'(x)
-}
-// GELU (erf form) in the forward bf16 epilogues, cheaper than the degree-12 Horner chain: Phi(x)
-// as a logistic of an odd quintic, GELU(x) ~= x * sigmoid(x (c0 + c1 x^2 + c2 x^4)) with x clamped
-// to [-9, 9] inside the polynomial (its fitted range; Phi(9) = 1 - 1e-19). Minimax fit of the GELU
-// error over all x: max abs error 2.5e-5 (the bf16 quantum near 1 is 3.9e-3). Cost per element:
-// med3 + 4 FMA-class + exp2 + rcp (the Horner form: 14 packed FMAs per PAIR, 8-cycle issue each).
+// GELU (erf form) in the forward bf16 epilogues: Phi(x) as a logistic of an odd quintic,
+// GELU(x) ~= x * sigmoid(x (c0 + c1 x^2 + c2 x^4)) with x clamped to [-9, 9] inside the polynomial
+// (its fitted range; Phi(9) = 1 - 1e-19). Max abs error 2.54e-5 (at x ~ 3.06) on the tested
+// domain, the finite bf16 values with |x| <= 8192 (tests/test_act_curves_gpu.py sweeps all of
+// them through every epilogue). Outside it only finiteness holds: for x < -9 the result is
+// x * 2.3e-12, not 0, which is harmless at 8192 and wrong at 1e30. Cost per element: med3 + 4
+// FMA-class + exp2 + rcp.
 __device__ __forceinline__ float gelu_sig(float x) {
   constexpr float L2E = 1.4426950408889634f;
   constexpr float K0 = -1.59501577f * L2E, K1 = -7.40112921e-2f * L2E, K2 = 7.03033584e-4f * L2E;
@@ -209,14 +205,6 @@ __device__ __forceinline__ float gelu_sig_grad(float x) {
   const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(q));
   const float dp = fmaf(x2, fmaf(x2, 5.f * C2, 3.f * C1), C0);
   return fmaf(xc * fmaf(-sg, sg, sg), dp, sg);
-}
-__device__ __forceinline__ f32x2 gelu_bwd_pair(f32x2 x) {
-  constexpr float c[13] = {1.421341449e-01f, -7.509786636e-02f, 6.654060632e-02f, -7.212746888e-02f,
-                           8.076252043e-02f, -8.158523589e-02f, 7.798881084e-02f, -7.819437981e-02f,
-                           5.708414689e-02f, -1.684123091e-02f, 1.213573292e-02f, -2.509075962e-02f,
-                           1.229602005e-02f};
-  f32x2 xc;
-  return gelu_poly_pair(x, c, xc);
 }
 
 // --- dropout: counter-based mask (no stored masks; fwd and bwd regenerate the same bits) ---

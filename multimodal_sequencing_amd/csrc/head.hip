@@ -56,10 +56,12 @@ __global__ __launch_bounds__(256) void pointer_fwd_kernel(int B, int N, int H,
     for (int j = 0; j < N; ++j) mx = fmaxf(mx, e[j]);
     float s = 0.f;
     for (int j = 0; j < N; ++j) s += expf(e[j] - mx);
-    const float lse = mx + logf(s);
-    for (int j = 0; j < N; ++j) logp[((int64_t)b * N + t) * N + j] = e[j] - lse;
+    // (e - mx) - log(sum), not e - (mx + log(sum)): with every entry of a row masked mx is -1e9,
+    // whose fp32 quantum (64) swallows log(sum) and gave logp = 0 instead of -log(N)
+    const float ls = logf(s);
+    for (int j = 0; j < N; ++j) logp[((int64_t)b * N + t) * N + j] = (e[j] - mx) - ls;
     const int tg = (int)target[(int64_t)b * N + t];
-    nll[(int64_t)b * N + t] = t < L ? -(e[tg] - lse) : 0.f;  // :1126-1135
+    nll[(int64_t)b * N + t] = t < L ? -((e[tg] - mx) - ls) : 0.f;  // :1126-1135
   }
 }
 
