@@ -747,6 +747,33 @@ mmseq_status mmseq_xent_bwd(int M, int V, void* logits, int64_t ld, const int64_
                             const float* g, mmseq_dtype dtype, mmseq_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Masked-LM evaluation in the forward's one pass (the counterpart of run_pretraining.py:377-511,
+ * whose "{task}_perplexity" is a TODO and which reports no accuracy): logits, labels, ld and the
+ * alignment rule as mmseq_xent_fwd; 0 <= k <= MMSEQ_XENT_EVAL_MAX_K, else MMSEQ_EINVAL with
+ * nothing launched. Candidates are ordered by (value descending, column ascending), values
+ * compared as float (-0.0 ties with +0.0): a total order, so no output depends on a merge order.
+ *  lse[r], loss_row[r]: the bits mmseq_xent_fwd writes for the same buffer (same traversal, same
+ *       wave-then-workgroup merge), 0 for ignored rows and NaN for any other label outside [0, V).
+ *  rank[r] = #{c : x[c] > x[lab]} + #{c < lab : x[c] == x[lab]}, -1 for an ignored row or an
+ *       invalid label (nothing is read for either).
+ *  topk_idx[r][0..k), topk_logit[r][0..k): the k first candidates of EVERY row (fill-mask needs no
+ *       label); entries past V are (-1, -inf). k == 0: both may be NULL, nothing is written.
+ *       rank == 0 <=> topk_idx[r][0] == label; 0 <= rank < k <=> the label is among the k.
+ *  totals (double[4], NULL skips it): [0] += sum of loss_row over the kept rows, [1] += kept rows,
+ *       [2] += rows with rank 0, [3] += rows with 0 <= rank < k; one workgroup, fixed order, no
+ *       atomics. An evaluation loop accumulates over its batches and reads 32 bytes back once.
+ * mmseq_xent_mean: stats[0] = sum(loss_row) / count, stats[1] = count over the kept rows, the
+ *       reduction mmseq_xent_fwd ends with (same bits), for loss_row written by mmseq_xent_eval.
+ * ------------------------------------------------------------------------------------------ */
+#define MMSEQ_XENT_EVAL_MAX_K 8
+mmseq_status mmseq_xent_eval(int M, int V, const void* logits, int64_t ld, const int64_t* labels,
+                             int64_t ignore_index, int k, float* lse, float* loss_row,
+                             int32_t* rank, int32_t* topk_idx, float* topk_logit, double* totals,
+                             mmseq_dtype dtype, mmseq_stream stream);
+mmseq_status mmseq_xent_mean(int M, const float* loss_row, const int64_t* labels,
+                             int64_t ignore_index, float* stats, mmseq_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pretraining inputs on device (text+image stage): csrc/inputs.hip.
  *
  * mlm_mask: trainers/train_utils.py:19-66 mask_tokens_sentence on input_ids [B][L] IN PLACE, with

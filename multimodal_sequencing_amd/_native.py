@@ -203,6 +203,9 @@ _SIGS = {
                                                            ctypes.c_int, _vp]),
     "mmseq_xent_bwd": (ctypes.c_int, [ctypes.c_int] * 2 + [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp,
                                                            ctypes.c_int, _vp]),
+    "mmseq_xent_eval": (ctypes.c_int, [ctypes.c_int] * 2 + [_vp, _c_i64, _vp, _c_i64, ctypes.c_int] +
+                        [_vp] * 6 + [ctypes.c_int, _vp]),
+    "mmseq_xent_mean": (ctypes.c_int, [ctypes.c_int, _vp, _vp, _c_i64, _vp, _vp]),
     "mmseq_mlm_mask": (ctypes.c_int, [ctypes.c_int] * 2 + [_vp, _vp] + [_c_i64] * 5 +
                        [ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32, _vp]),
     "mmseq_subsample_text": (ctypes.c_int, [ctypes.c_int] * 4 + [_vp] * 5 + [_c_i64] * 3 +
@@ -803,6 +806,8 @@ def _xent_args(what, logits, V, labels, lse, stats):
     if labels.dtype != torch.int64 or labels.numel() != M or not labels.is_contiguous():
         raise ValueError(f"{what}: labels must be contiguous int64 [{M}]")
     for t, n, name in ((lse, M, "lse"), (stats, 2, "stats")):
+        if t is None and name == "stats" and what == "xent_eval":
+            continue  # optional there
         if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
             raise ValueError(f"{what}: {name} must be contiguous f32 [{n}]")
     return M, ld
@@ -828,6 +833,40 @@ def xent_bwd(logits, V, labels, ignore_index, lse, stats, g=None):
         raise ValueError("xent_bwd: g must be one f32 on the device")
     _check_shape(lib().mmseq_xent_bwd(M, V, _p(logits), ld, _p(labels), ignore_index, _p(lse),
                                       _p(stats), _p(g), dt(logits), _stream()), "mmseq_xent_bwd")
+
+
+XENT_EVAL_MAX_K = 8  # MMSEQ_XENT_EVAL_MAX_K
+
+
+def xent_eval(logits, V, labels, ignore_index, k, lse, loss_row, rank, topk_idx=None,
+              topk_logit=None, totals=None, stats=None):
+    """The forward's pass with the evaluation quantities (mmseq_xent_eval): lse / loss_row f32 [M]
+    (the bits xent_fwd writes), rank int32 [M], topk_idx int32 [M][k] and topk_logit f32 [M][k]
+    (both may be None with k == 0) in the order (value descending, column ascending), totals
+    f64 [4] or None, accumulated. `stats` f32 [2] or None: (mean loss over the kept rows, their
+    count) with xent_fwd's bits, reduced from loss_row (mmseq_xent_mean)."""
+    M, ld = _xent_args("xent_eval", logits, V, labels, lse, stats)
+    k = int(k)
+    if not 0 <= k <= XENT_EVAL_MAX_K:
+        raise ValueError(f"xent_eval: k = {k} outside [0, {XENT_EVAL_MAX_K}]")
+    _dev(loss_row, rank, topk_idx, topk_logit, totals)
+    for t, d, name in ((loss_row, torch.float32, "loss_row"), (rank, torch.int32, "rank")):
+        if t.dtype != d or t.numel() != M or not t.is_contiguous():
+            raise ValueError(f"xent_eval: {name} must be contiguous {d} [{M}]")
+    for t, d, name in ((topk_idx, torch.int32, "topk_idx"), (topk_logit, torch.float32, "topk_logit")):
+        if t is None and k == 0:
+            continue
+        if t is None or t.dtype != d or tuple(t.shape) != (M, k) or not t.is_contiguous():
+            raise ValueError(f"xent_eval: {name} must be contiguous {d} [{M}][{k}]")
+    if totals is not None and (totals.dtype != torch.float64 or totals.numel() != 4 or
+                               not totals.is_contiguous()):
+        raise ValueError("xent_eval: totals must be contiguous f64 [4]")
+    _check_shape(lib().mmseq_xent_eval(M, V, _p(logits), ld, _p(labels), ignore_index, k, _p(lse),
+                                       _p(loss_row), _p(rank), _p(topk_idx), _p(topk_logit),
+                                       _p(totals), dt(logits), _stream()), "mmseq_xent_eval")
+    if stats is not None:
+        _check(lib().mmseq_xent_mean(M, _p(loss_row), _p(labels), ignore_index, _p(stats),
+                                     _stream()), "mmseq_xent_mean")
 
 
 def _i64_dev(what, name, t, shape):

@@ -1277,3 +1277,61 @@ class MlmLossFn:
         loss, _ = VocabXentFn.apply(t, anchor, word_store, wname, head_store, prefix + "bias", lab,
                                     ignore_index)
         return loss
+
+
+# ================================================================================================
+# evaluation of the masked-LM head: the loss's one pass, with rank and the k best words
+# ================================================================================================
+def vocab_eval(h, wstore, wname, bstore, bname, labels, ignore_index, k, totals=None):
+    """The evaluation twin of VocabXentFn.forward, under no_grad and with nothing saved: the tied
+    decoder GEMM into the row-padded logit buffer exactly as there, then ONE pass of
+    mmseq_xent_eval. h [M][H], labels int64 [M] (ignore_index: no label, rank -1, top-k still
+    written). Returns a dict of device tensors: lse, loss_row (the forward's bits), rank int32 [M],
+    topk_idx int32 [M][k], topk_logit f32 [M][k] in the order (value descending, word id
+    ascending), mean_loss (the forward's stats[0] bits). `totals` f64 [4] accumulates (sum of NLL,
+    labelled rows, rank 0, rank < k) on the device."""
+    with torch.no_grad():
+        h = h.detach().contiguous()
+        Mc, H = h.shape
+        W = wstore.w(wname)
+        V = W.shape[0]
+        ld = (V + 63) // 64 * 64
+        logits = torch.empty(Mc, ld, device=h.device, dtype=h.dtype)
+        N.gemm(h, W, logits, Mc, V, H, ldc=ld, bias=bstore.f32(bname))
+        dev = h.device
+        out = {"lse": torch.empty(Mc, device=dev), "loss_row": torch.empty(Mc, device=dev),
+               "rank": torch.empty(Mc, dtype=torch.int32, device=dev),
+               "topk_idx": torch.empty(Mc, k, dtype=torch.int32, device=dev),
+               "topk_logit": torch.empty(Mc, k, device=dev)}
+        stats = torch.empty(2, device=dev)
+        N.xent_eval(logits, V, labels.contiguous(), ignore_index, k, out["lse"], out["loss_row"],
+                    out["rank"], out["topk_idx"] if k else None, out["topk_logit"] if k else None,
+                    totals, stats)
+        out["mean_loss"] = stats[0].clone()
+    return out
+
+
+def mlm_eval(lang_output, labels, ignore_index, head_store, word_store, k, rows=None, totals=None,
+             wname="embeddings.word_embeddings.weight", prefix="cls.predictions."):
+    """The evaluation twin of MlmLossFn.apply: gather the labelled rows, cls.predictions.transform,
+    then vocab_eval. Returns vocab_eval's dict plus `rows` (int32: the flat source row of each
+    labelled position, in row order) and `labels` (int64, their gold ids). labels=None evaluates
+    EVERY row (fill-mask over whole sequences): rank is -1 and the loss 0 throughout."""
+    x = lang_output
+    with torch.no_grad():
+        if labels is None and rows is None:
+            n = x.numel() // x.shape[-1]
+            src = torch.arange(n, dtype=torch.int32, device=x.device)
+            lab = torch.full((n,), int(ignore_index), dtype=torch.int64, device=x.device)
+        else:
+            src, lab = labelled_rows(labels, ignore_index, x.device) if rows is None else rows
+        hc = torch.empty(src.numel(), x.shape[-1], device=x.device, dtype=x.dtype)
+        N.rows_gather_fwd(x.detach(), src, None, hc)
+        anchor = None
+        t = LinearFn.apply(hc, anchor, head_store, prefix + "transform.dense.weight",
+                           prefix + "transform.dense.bias", GELU)
+        t = LayerNormFn.apply(t, anchor, head_store, prefix + "transform.LayerNorm", 1e-12)
+        out = vocab_eval(t, word_store, wname, head_store, prefix + "bias", lab, ignore_index, k,
+                         totals)
+    out["rows"], out["labels"] = src, lab
+    return out

@@ -56,6 +56,7 @@ patch_based_mrm_classification (MRM) the model was built with, and the masked-LM
 stream); total = objective + MLM, losses = [[objective, mlm]].
 """
 import copy
+import os
 from types import SimpleNamespace
 
 import numpy as np
@@ -186,14 +187,15 @@ def _raise_bad_stories(bad):
 _MASK_CALLS = [0]  # process-wide: mask_tokens_sentence(seed=None) never repeats a key
 
 
-def mask_tokens_sentence(inputs, tokenizer, args, seed=None, device="cuda"):
+def mask_tokens_sentence(inputs, tokenizer, args, seed=None, device="cuda", stream_id=None):
     """Drop-in for trainers/train_utils.py:19-66 on the device (kernels.mlm_mask): 80 % [MASK],
     10 % random word, 10 % unchanged over the tokens selected with args.mlm_probability; reads
     tokenizer.pad_token / mask_token (convert_tokens_to_ids), len(tokenizer), args.cls_id and
     args.mlm_ignore_index. `inputs`: int64 [B][L]; a device tensor is masked IN PLACE, a host one
     is copied to `device` first. Returns (inputs, labels), both on the device. seed=None draws a
     fresh key from a process-wide counter (successive calls differ); an explicit seed reproduces
-    the bits."""
+    the bits. `stream_id` (with an explicit seed) selects another counter stream of that seed: the
+    evaluation loop masks step s on stream 2 + s; None is stream 0."""
     pad_id = tokenizer.convert_tokens_to_ids(tokenizer.pad_token)
     mask_id = tokenizer.convert_tokens_to_ids(tokenizer.mask_token)
     t = torch.as_tensor(inputs)
@@ -201,10 +203,13 @@ def mask_tokens_sentence(inputs, tokenizer, args, seed=None, device="cuda"):
         t = t.to(device, torch.int64).contiguous()
     if t.dtype != torch.int64 or t.dim() != 2 or not t.is_contiguous():
         raise ValueError("mask_tokens_sentence: inputs must be contiguous int64 [B][L]")
-    stream_id = 0
     if seed is None:
+        if stream_id is not None:
+            raise ValueError("mask_tokens_sentence: stream_id needs an explicit seed")
         _MASK_CALLS[0] += 1
         seed, stream_id = _MASK_CALLS[0], 1  # stream 1: apart from every explicit seed's stream 0
+    elif stream_id is None:
+        stream_id = 0
     labels = K.mlm_mask(t, pad_id, args.cls_id, mask_id, len(tokenizer), args.mlm_ignore_index,
                         args.mlm_probability, seed, stream_id)
     return t, labels
@@ -317,22 +322,23 @@ class LXRTPretraining(nn.Module):
         return {}, []
 
     # ------------------------------------------------------------------------------------
-    def draw(self, B, N, Tv):
+    def draw(self, B, N, Tv, rng=None):
         """The reference's np.random draws (:1981, :983-987, :2322-2323) for a batch of B
-        stories of N images with Tv visual tokens (1 + 2 g^2)."""
+        stories of N images with Tv visual tokens (1 + 2 g^2), from `rng` (default self.rng)."""
+        rng = rng or self.rng
         per = Tv // 2  # visn_per_seq_len (:955)
         sub_idx, mask_idx, shuffle = [], [], []
         for _ in range(B):
-            sub_idx.append(sorted(self.rng.choice(N, 2, replace=False)))
+            sub_idx.append(sorted(rng.choice(N, 2, replace=False)))
         for _ in range(B):
             m = []
             for start in range(1, Tv, per):
-                m += sorted(self.rng.choice(list(range(start, start + per)), self.MASK_NUM,
+                m += sorted(rng.choice(list(range(start, start + per)), self.MASK_NUM,
                                             replace=False))
             mask_idx.append(m)
         for _ in range(B):
             idx = np.arange(self.MASK_NUM * 2)
-            self.rng.shuffle(idx)
+            rng.shuffle(idx)
             shuffle.append(idx)
         return {"sub_idx": np.asarray(sub_idx, np.int64), "mask_idx": np.asarray(mask_idx, np.int64),
                 "shuffle": np.asarray(shuffle, np.int64)}
@@ -416,6 +422,36 @@ class LXRTPretraining(nn.Module):
         """:1734-2484 for the image-only MRM objective. `input_ids` may be the batch dict
         (input_ids, attention_mask, images [B, N, 3, R, R]); `draws` the explicit random
         choices (else drawn from self.rng)."""
+        return self._forward_any(input_ids, token_type_ids, attention_mask, masked_lm_labels,
+                                 visual_feats, draws, None)
+
+    def evaluate_batch(self, batch, topk=5, totals=None):
+        """One evaluation batch of either stage: (loss, losses, answer, stats) under no_grad, the
+        first three with the bits `model(batch)` gives on the same batch and draws under no_grad
+        in eval mode (the same kernels run; only the masked-LM loss's pass is the evaluating
+        instantiation, mmseq_xent_eval). Raises in train mode (dropout would make the statistics
+        those of another network). `batch`: the dict `forward` takes. stats, text+image stage:
+          mlm                kernels.mlm_eval's dict over the labelled rows (rows, labels, lse,
+                             loss_row, rank, topk_idx / topk_logit [rows][topk], mean_loss)
+          seq_len            Lt: mlm["rows"] = story * Lt + position in the sub-sampled text
+          objective, objective_logits, objective_labels, objective_loss
+          objective_correct, objective_count   device int64 scalars (arg-max of the head's scores:
+                             [B] decisions for ISP / PISP, [B][10] for MRM)
+        `totals` (f64 [4] on the device) accumulates (sum of NLL, labelled tokens, rank 0,
+        rank < topk) over the calls. The image-only stage has no masked-LM term: its stats hold the
+        MRM head's objective_* entries only."""
+        if self.training:
+            raise RuntimeError("evaluate_batch needs the model in eval mode: call model.eval()")
+        if not isinstance(batch, dict):
+            raise TypeError("evaluate_batch takes the batch dict that forward takes")
+        ev = {"topk": int(topk), "totals": totals, "stats": {}}
+        with torch.no_grad():
+            loss, losses, answer = self._forward_any(batch, None, None, None, None, None, ev)
+        return loss, losses, answer, ev["stats"]
+
+    def _forward_any(self, input_ids, token_type_ids, attention_mask, masked_lm_labels,
+                     visual_feats, draws, ev):
+        """forward's body; `ev` (evaluate_batch's request) also collects the statistics."""
         if isinstance(input_ids, dict):
             batch = input_ids
             visual_feats = batch.get("images")
@@ -426,7 +462,7 @@ class LXRTPretraining(nn.Module):
                 masked_lm_labels = batch.get("masked_lm_labels")
         if not self.multimodal_img_part:
             return self._forward_mm(input_ids, token_type_ids, attention_mask, masked_lm_labels,
-                                    visual_feats, draws)
+                                    visual_feats, draws, ev)
         images = visual_feats.to(self.device_, torch.float32).contiguous()
         B, Nimg = images.shape[:2]
         inner = self.bert
@@ -491,10 +527,12 @@ class LXRTPretraining(nn.Module):
         ce = -logp.gather(-1, labels[:, :, None]).squeeze(-1).mean(-1)  # CrossEntropyLoss per story
         mrm = ce.sum() * self.MRM_SCALE
         losses = mrm.detach().view(1, 1)
+        if ev is not None:
+            ev["stats"].update(_objective_stats(MRM, scores, labels, mrm))
         return mrm, losses, answer.detach()
 
     def _forward_mm(self, input_ids, token_type_ids, attention_mask, masked_lm_labels, images,
-                    draws):
+                    draws, ev=None):
         """:1734-2484 for the text+image stage: one objective per batch + the masked-LM term.
         Returns (total_loss, [[objective_loss, mlm_loss]], answer_score). A device `input_ids`
         takes the device input path (attention_mask, token_type_ids and masked_lm_labels must then
@@ -617,8 +655,16 @@ class LXRTPretraining(nn.Module):
             scores = self._lin(pooled, st, obj + "_mlp").float()
             obj_loss = torch.nn.functional.cross_entropy(scores, obj_labels.to(dev))
         self.last_objective_logits, self.last_objective_labels = scores.detach(), obj_labels
-        mlm = K.MlmLossFn.apply(lang, labels, self.mlm_ignore_index, self._anchor, st, st_in,
-                                rows=mlm_rows)
+        if ev is None:
+            mlm = K.MlmLossFn.apply(lang, labels, self.mlm_ignore_index, self._anchor, st, st_in,
+                                    rows=mlm_rows)
+        else:  # the same gather, transform and decoder GEMM; the loss's pass also ranks
+            stats = ev["stats"]
+            stats["mlm"] = K.mlm_eval(lang, labels, self.mlm_ignore_index, st, st_in, ev["topk"],
+                                      rows=mlm_rows, totals=ev["totals"])
+            stats["seq_len"] = Lt
+            stats.update(_objective_stats(obj, scores, obj_labels.to(dev), obj_loss))
+            mlm = stats["mlm"]["mean_loss"]
         total = obj_loss + mlm
         losses = torch.stack([obj_loss.detach(), mlm.detach()]).view(1, 2)
         return total, losses, answer.detach()
@@ -637,6 +683,130 @@ class LXRTPretraining(nn.Module):
             N.gemm(h.detach(), Wd, out, h.shape[0], V, h.shape[-1], ldc=ldc,
                    bias=st.f32(p + "bias"))
         return out[:, :V]
+
+
+def _objective_stats(obj, scores, labels, loss):
+    """Accuracy of an objective head from its scores ([B][2] for ISP / PISP, [B][10][10] for MRM)
+    and labels ([B] / [B][10]); tiny, so the arg-max stays a torch op as the head's loss does."""
+    correct = (scores.detach().argmax(-1) == labels).sum()
+    return {"objective": obj, "objective_logits": scores.detach(), "objective_labels": labels,
+            "objective_loss": loss.detach(), "objective_correct": correct,
+            "objective_count": torch.tensor(labels.numel(), device=correct.device)}
+
+
+def fill_mask(model, batch, k=5, tokenizer=None):
+    """What the model puts at the masks of one text+image batch (the dict `forward` takes, masked
+    by mask_tokens_sentence). Per labelled position, in row order, a dict of device tensors:
+    story [n], position [n] (in the sub-sampled text), gold [n], ids [n][k] ordered by (logit
+    descending, id ascending), probs [n][k] = exp(topk_logit - lse), rank [n], loss_row [n]; with
+    a tokenizer also tokens / gold_tokens (convert_ids_to_tokens). A convenience over
+    evaluate_batch."""
+    _, _, _, stats = model.evaluate_batch(batch, topk=k)
+    if "mlm" not in stats:
+        raise ValueError("fill_mask needs the text+image stage (the image-only stage has no "
+                         "masked-LM head in its loss)")
+    m, Lt = stats["mlm"], stats["seq_len"]
+    rows = m["rows"].long()
+    out = {"story": rows // Lt, "position": rows % Lt, "gold": m["labels"],
+           "ids": m["topk_idx"].long(), "probs": torch.exp(m["topk_logit"] - m["lse"][:, None]),
+           "rank": m["rank"], "loss_row": m["loss_row"]}
+    if tokenizer is not None:
+        out["tokens"] = [tokenizer.convert_ids_to_tokens(r) for r in out["ids"].tolist()]
+        out["gold_tokens"] = tokenizer.convert_ids_to_tokens(out["gold"].tolist())
+    return out
+
+
+def pretrain_evaluate(args, model, load_and_cache_examples, tokenizer, prefix="", seed=0, topk=5):
+    """trainers/run_pretraining.py:377-511 (`evaluate`, as scripts/wikihow_pretrain.sh runs it with
+    --do_eval --evaluate_during_training --max_eval_steps 200) for LXRTPretraining: the per-task
+    loop (:384-386), SequentialSampler and eval_batch_size = per_gpu_eval_batch_size *
+    max(1, n_gpu) (:391-395), model.eval() (:416), the batch to the device (:417), masking by
+    mask_tokens_sentence for the text+image stage (:433-437), max_eval_steps (:480-483), the mean
+    of the per-batch losses (:485) and the results written sorted as "%s = %s\n" into
+    <output_dir>/<prefix>/eval_results.txt (:502-509).
+    `load_and_cache_examples(args, [task], tokenizer, evaluate=True)` returns a map-style dataset
+    of tuples (input_ids, attention_mask, token_type_ids, labels, ..., images).
+
+    Beyond the reference, whose :493-497 writes "{task}_perplexity": 0.0 under "# TODO:
+    Perplexity." and reports no accuracy: {task}_perplexity = exp(sum of NLL / labelled tokens)
+    over the whole evaluation (0.0 for the image-only stage, which has no masked-LM term),
+    {task}_mlm_loss, _mlm_acc, _mlm_acc_top{topk}, _mlm_tokens, and per objective drawn at least
+    once {task}_{objective}_acc, _loss, _batches.
+
+    An evaluation is a pure function of (weights, data, seed): step s is masked with `seed` on
+    counter stream 2 + s and the model's draws come from a local RandomState(seed), so model.rng
+    and the process-wide mask counter are untouched and training resumes on the stream it would
+    have had. Everything accumulates on the device and is read back once per task."""
+    from torch.utils.data import DataLoader, SequentialSampler
+    results = {}
+    dev = model.device_
+    mm = not model.multimodal_img_part
+    objectives = list(model.multimodal_pretrain_objectives)
+    for task, out_dir in zip(args.task_names, [args.output_dir] * len(args.task_names)):
+        dataset = load_and_cache_examples(args, [task], tokenizer, evaluate=True)
+        if not os.path.exists(out_dir) and getattr(args, "local_rank", -1) in (-1, 0):
+            os.makedirs(out_dir)
+        args.eval_batch_size = args.per_gpu_eval_batch_size * max(1, getattr(args, "n_gpu", 1))
+        loader = DataLoader(dataset, sampler=SequentialSampler(dataset),
+                            batch_size=args.eval_batch_size)
+        rng = np.random.RandomState(seed)
+        totals = torch.zeros(4, dtype=torch.float64, device=dev)
+        loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
+        # per objective: correct decisions, decisions, summed loss, batches
+        per_obj = torch.zeros(len(objectives), 4, dtype=torch.float64, device=dev)
+        steps = 0
+        for batch in loader:
+            model.eval()
+            images = batch[-1]
+            B, Nimg = images.shape[:2]
+            g = images.shape[-1] // model.bert.vision["patch"]
+            inputs = {"images": images}
+            if mm:
+                ids = batch[0].to(dev, torch.int64).contiguous()
+                ids, lm_labels = mask_tokens_sentence(ids, tokenizer, args, seed=seed,
+                                                      stream_id=2 + steps)
+                inputs.update(input_ids=ids, masked_lm_labels=lm_labels,
+                              attention_mask=batch[1].to(dev))
+                if getattr(args, "replace_token_type_embeddings", False) and \
+                        getattr(args, "model_type", "roberta") in ("bert", "roberta"):
+                    inputs["token_type_ids"] = batch[2].to(dev)
+                inputs["draws"] = model.draw_mm(B, Nimg, 1 + 2 * g * g, rng=rng)
+            else:
+                inputs["input_ids"] = batch[0]
+                inputs["draws"] = model.draw(B, Nimg, 1 + 2 * g * g, rng=rng)
+            loss, _, _, stats = model.evaluate_batch(inputs, topk=topk,
+                                                     totals=totals if mm else None)
+            loss_sum += loss.double()
+            o = objectives.index(stats["objective"])
+            per_obj[o] += torch.stack([stats["objective_correct"].double(),
+                                       stats["objective_count"].double(),
+                                       stats["objective_loss"].double(),
+                                       torch.ones((), dtype=torch.float64, device=dev)])
+            steps += 1
+            if getattr(args, "max_eval_steps", 0) > 0 and steps >= args.max_eval_steps:
+                break
+        # the one read-back of the task
+        flat = torch.cat([loss_sum.view(1), totals, per_obj.view(-1)]).tolist()
+        loss_sum_h, tot, po = flat[0], flat[1:5], np.asarray(flat[5:]).reshape(-1, 4)
+        result = {f"{task}_loss": loss_sum_h / max(steps, 1), f"{task}_perplexity": 0.0}
+        if mm:
+            tokens = tot[1]
+            nll = tot[0] / tokens if tokens else float("nan")
+            result.update({f"{task}_perplexity": float(np.exp(nll)), f"{task}_mlm_loss": nll,
+                           f"{task}_mlm_acc": tot[2] / tokens if tokens else float("nan"),
+                           f"{task}_mlm_acc_top{topk}": tot[3] / tokens if tokens else float("nan"),
+                           f"{task}_mlm_tokens": int(tokens)})
+        for name, (correct, count, lsum, nb) in zip(objectives, po):
+            if nb:
+                result.update({f"{task}_{name}_acc": correct / count,
+                               f"{task}_{name}_loss": lsum / nb, f"{task}_{name}_batches": int(nb)})
+        results.update(result)
+    out_file = os.path.join(out_dir, prefix, "eval_results.txt")
+    os.makedirs(os.path.dirname(out_file), exist_ok=True)
+    with open(out_file, "w") as wr:
+        for key in sorted(results):
+            wr.write("%s = %s\n" % (key, str(results[key])))
+    return results
 
 
 def build_config2(device="cuda", dtype=torch.bfloat16, seed=0, vision="ViT-B/16", joint=None):
