@@ -100,45 +100,8 @@ class fp8_forward:
             _FP8["cache"].clear()
 
 
-def _kind_sites(kind):
-    """The fp8 GEMM sites on for layer kind "vit" / "joint" under the current fp8_forward()."""
-    s = _FP8["sites"]
-    if s is None:
-        return frozenset(FP8_SITES)
-    return frozenset(x for x in FP8_SITES if x in s or f"{kind}.{x}" in s)
-
-
-def _mixed(kind):
-    """An eval forward of a layer of `kind` under fp8_forward(sites=...) that mixes fp8 and bf16
-    GEMMs (the unfused mixed-placement path). A kind with all four sites on keeps the fused MX-fp8
-    path, a kind with none the bf16 one (e.g. sites = the four "vit.*": the ViT on the fp8 MFMA at
-    full speed, the joint encoder in bf16)."""
-    if not _FP8["on"] or _FP8["sites"] is None:
-        return False
-    return 0 < len(_kind_sites(kind)) < len(FP8_SITES)
-
-
-def _f8_kind(kind):
-    """fp8 eval GEMMs for this layer kind at all (fused path): off when its sites are all off."""
-    return _FP8["on"] and (_FP8["sites"] is None or len(_kind_sites(kind)) == len(FP8_SITES))
-
-
-def _lin_site(kind, site, st, x, W, bias=None, act=0, resid=None):
-    """Mixed placement: x W^T (+ bias, act, resid) with bf16 output, on the MX-fp8 MFMA when
-    `site` (or `kind.site`) is in the fp8_forward sites (activation quantised by
-    mmseq_quant_mxfp8, the weight once per store version), else the bf16 GEMM."""
-    sites = _FP8["sites"]
-    if site in sites or f"{kind}.{site}" in sites:
-        R = x.numel() // x.shape[-1]
-        out = torch.empty(R, W.shape[0], device=x.device, dtype=torch.bfloat16)
-        N.gemm_mxfp8(N.quant_mxfp8(x.reshape(R, -1)), _fp8_weight(st, W), out, bias=bias, act=act,
-                     resid=resid.reshape(R, -1) if resid is not None else None)
-        return out
-    return _linear(x, W, bias=bias, act=act, resid=resid)
-
-
 def _fp8_bwd_done(f8):
-    """End of a layer backward that ran its dgrads on the fp8 MFMA (ctx.f8dg, captured in the
+    """End of a layer backward that ran its dgrads on the fp8 MFMA (the engine chosen in the
     forward): when that backward runs after the fp8_forward() context has exited, the transposed
     weights' fp8 copies it quantised would stay in the cache until another context exits."""
     if f8 and not _FP8["on"]:
@@ -154,89 +117,220 @@ def _fp8_weight(st, W):
     return hit[2]
 
 
-def _f8(x, W, kind=None):
-    """The no-grad forward runs this GEMM on the fp8 MFMA: fp8_forward() on (for this layer kind:
-    all its sites, see fp8_forward(sites=...)), bf16, K and the output width multiples of 256 (the
-    256 x 256 8-phase kernel's MX-fp8 form), and a hidden width the fused MX-fp8 LayerNorm takes
-    (<= 1024)."""
-    K = x.shape[-1]
-    return ((_FP8["on"] if kind is None else _f8_kind(kind)) and x.dtype == torch.bfloat16
-            and K % 256 == 0 and W.shape[0] % 256 == 0 and K <= 1024 and x.is_contiguous())
+class _Act:
+    """An activation (or gradient) on its way to a GEMM: the bf16 / fp32 tensor `t`, its MX-fp8 copy
+    `q` (_native.MXFP8), or both. Producers fill in what their engine decides; a consumer GEMM
+    takes the form it runs on, so a layer body never asks which one exists."""
+    __slots__ = ("t", "q")
+
+    def __init__(self, t=None, q=None):
+        self.t, self.q = t, q
+
+    @property
+    def rows(self):
+        return self.t.shape[0] if self.t is not None else self.q.rows
 
 
-def _f8_train(x, *Ws):
-    """The training forward of a layer runs its GEMMs on the fp8 MFMA: fp8_forward(training=True),
-    every GEMM of the layer in the 8-phase MX-fp8 form (K and widths multiples of 256), >= 256 rows."""
-    return (_FP8["train"] and x.dtype == torch.bfloat16 and x.shape[0] >= 256 and x.shape[-1] <= 1024
-            and x.is_contiguous() and all(W.shape[0] % 256 == 0 and W.shape[1] % 256 == 0 for W in Ws))
+def _act_in(x):
+    """A layer's input x with the MX-fp8 copy the previous layer's last LayerNorm attached
+    (_Engine.ln attach=True), if x has not been modified since. The copy is detached from x here:
+    x itself is saved for backward, and an attribute would keep the fp8 copy alive with it until
+    then; a layer that does not read the copy drops it with the handle."""
+    hit = x.__dict__.pop("_mx", None)
+    return _Act(x, hit[0] if hit is not None and hit[1] == x._version else None)
 
 
-def _mx(x, hit=None):
-    """The MX-fp8 copy of activation x: the one its producer (a fused LayerNorm) attached, if x has
-    not been modified since, else a quantisation pass (mmseq_quant_mxfp8). The attached copy is
-    detached on use (or passed in as `hit`, already detached by the consumer): x itself is often
-    saved for backward, and an attribute would keep the fp8 copy alive with it until then."""
-    if hit is None:
-        hit = x.__dict__.pop("_mx", None)
-    if hit is not None and hit[1] == x._version:
-        return hit[0]
-    return N.quant_mxfp8(x.view(-1, x.shape[-1]))
+class _Engine:
+    """How one layer call runs its four GEMMs (FP8_SITES), two LayerNorms and attention, chosen
+    once per forward by _engine() and read back from ctx by the backward.
 
+    f8: the GEMM sites on the fp8 MFMA (the others in bf16 / fp32). emit: the sites whose operand
+    its PRODUCER also writes in MX-fp8 in the same pass (LayerNorm, attention, FC1's epilogue); at
+    an fp8 site outside emit the GEMM quantises its input itself (mmseq_quant_mxfp8: the same
+    numbers, the fused producers are bit-identical to bf16 output + quantiser). save: a training
+    forward, every producer also writes the bf16 tensor the backward reads (and the GELU
+    pre-activation, the attention keep bits). f8dg: the backward's data-gradient GEMMs on the fp8
+    MFMA too (weight gradients stay bf16)."""
 
-def _lin8(st, x, W, bias=None, resid=None, xq=None):
-    """bf16 act-free x W^T + bias (+ resid) with both operands in MX-fp8 (the activation's copy
-    from _mx or xq, the weight quantised once per store version)."""
-    xq = xq if xq is not None else _mx(x)
-    out = torch.empty(xq.rows, W.shape[0], device=W.device, dtype=torch.bfloat16)
-    N.gemm_mxfp8(xq, _fp8_weight(st, W), out, bias=bias,
-                 resid=resid.view(xq.rows, -1) if resid is not None else None)
-    return out
+    def __init__(self, st, f8=(), emit=(), save=False, f8dg=False):
+        self.st, self.f8, self.emit = st, frozenset(f8), frozenset(emit)
+        self.save, self.f8dg = save, f8dg
 
+    def _q(self, a):
+        """a's MX-fp8 copy: the one its producer wrote, else a quantisation pass."""
+        return a.q if a.q is not None else N.quant_mxfp8(a.t.view(-1, a.t.shape[-1]))
 
-def _ln8(x, gamma, beta, eps, y=None, mean=None, rstd=None, attach=False):
-    """LayerNorm of x whose output also leaves in MX-fp8 (mmseq_layernorm_fwd_mxfp8); with y the
-    bf16 output too. attach=True (a layer's output, consumed by the NEXT layer's first GEMM): the
-    MX-fp8 copy rides on y until that consumer's _mx detaches it. Copies the caller uses directly
-    are returned only: never attached to a tensor that goes into save_for_backward."""
-    q = N.layernorm_fwd_mxfp8(x.shape[0], x.shape[-1], x, gamma, beta, eps, y=y, mean=mean, rstd=rstd)
-    if y is not None and attach:
-        y._mx = (q, y._version)  # valid while y is unmodified (_mx checks the version)
-    return q
+    # -- forward ----------------------------------------------------------------------------------
+    def keep(self, *ts):
+        """What the backward reads of handles / tensors the forward is done with: their bf16 tensors
+        in a training forward, None otherwise (an eval forward lets go of them here)."""
+        out = tuple((t.t if isinstance(t, _Act) else t) if self.save else None for t in ts)
+        return out if len(out) > 1 else out[0]
 
-
-def _mlp_fwd(st, x, Wi, bi, act, Wo, bo, resid, lin, xq=None, kind=None):
-    """resid + FC2(act(FC1(x))) of a no-grad forward. Under fp8_forward(): with K and both widths
-    multiples of 256 both GEMMs run on the fp8 MFMA (FC1's epilogue writes FC2's MX-fp8 operand,
-    mmseq_gemm_mxfp8_q8); otherwise (K % 128 == 0) FC1 is the bf16 GEMM with that epilogue
-    (mmseq_gemm_mxfp8_out) and FC2 the fp8 GEMM."""
-    K, F = Wi.shape[1], Wi.shape[0]
-    if xq is not None:  # the input arrives in MX-fp8 only (fused LayerNorm)
-        q = N.gemm_mxfp8_q8(xq, _fp8_weight(st, Wi), bias=bi, act=act)
-        out = torch.empty(xq.rows, Wo.shape[0], device=Wi.device, dtype=torch.bfloat16)
-        N.gemm_mxfp8(q, _fp8_weight(st, Wo), out, bias=bo, resid=resid.view(xq.rows, -1))
-        return out
-    if ((_FP8["on"] if kind is None else _f8_kind(kind)) and x.dtype == torch.bfloat16 and K % 128 == 0
-            and F % 128 == 0 and x.is_contiguous() and resid.is_contiguous()):
-        R = x.numel() // K
-        if _f8(x, Wi) and F % 256 == 0 and Wo.shape[0] % 256 == 0:
-            q = N.gemm_mxfp8_q8(_mx(x), _fp8_weight(st, Wi), bias=bi, act=act)
+    def linear(self, site, a, W, bias=None, act=0, resid=None, drop=None, to=None, pre=False):
+        """dropout(act(a W^T + bias)) (+ resid) at GEMM site `site`, W [out][in] compute dtype (its
+        fp8 copy quantised once per store version) -> handle. to: the site that consumes the
+        output, if a GEMM. pre=True -> (handle, z), z the pre-activation the backward reads (None
+        outside training)."""
+        q8 = to in self.emit  # the epilogue writes the consumer's MX-fp8 operand
+        z = torch.empty(a.rows, W.shape[0], device=W.device, dtype=W.dtype) if pre and self.save else None
+        if site not in self.f8:
+            if q8:  # bf16 MFMA, MX-fp8 output only (eval FFN with K % 128: mmseq_gemm_mxfp8_out)
+                out = _Act(q=N.gemm_mxfp8_out(a.t, W, bias=bias, act=act))
+            else:
+                out = _Act(_linear(a.t, W, bias=bias, act=act, aux=z, resid=resid, drop=drop))
+        elif q8 and not self.save:  # eval: the output is only the next fp8 GEMM's operand
+            out = _Act(q=N.gemm_mxfp8_q8(self._q(a), _fp8_weight(self.st, W), bias=bias, act=act))
         else:
-            q = N.gemm_mxfp8_out(x.view(R, K), Wi, bias=bi, act=act)
-        out = torch.empty(R, Wo.shape[0], device=x.device, dtype=x.dtype)
-        N.gemm_mxfp8(q, _fp8_weight(st, Wo), out, bias=bo, resid=resid.view(R, -1))
-        return out
-    return lin(lin(x, Wi, bias=bi, act=act), Wo, bias=bo, resid=resid)
+            aq = self._q(a)
+            y = torch.empty(aq.rows, W.shape[0], device=W.device, dtype=torch.bfloat16)
+            if self.save:
+                out = _Act(y, N.gemm_mxfp8_ex(aq, _fp8_weight(self.st, W), y, bias=bias, act=act, aux=z,
+                                              resid=resid, drop=drop, q8=q8))
+            else:  # eval fp8 sites run without dropout (_engine)
+                N.gemm_mxfp8(aq, _fp8_weight(self.st, W), y, bias=bias, act=act, resid=resid)
+                out = _Act(y)
+        return (out, z) if pre else out
+
+    def ln(self, x, gamma, beta, eps, to, keep=False, attach=False):
+        """LayerNorm of x [R][C], the operand of the GEMM at site `to` -> (handle, mean, rstd).
+        keep: the caller reads the bf16 output too (a residual). attach (a layer's output, consumed
+        by the NEXT layer's first GEMM): the MX-fp8 copy rides on the bf16 tensor, valid while that
+        is unmodified (_act_in checks the version). Copies the caller uses directly come in the
+        handle only: never attached to a tensor that goes into save_for_backward."""
+        R, C = x.shape
+        mean = torch.empty(R, device=x.device)
+        rstd = torch.empty_like(mean)
+        y = torch.empty_like(x) if keep or self.save or to not in self.emit else None
+        q = None
+        if to in self.emit:
+            q = N.layernorm_fwd_mxfp8(R, C, x, gamma, beta, eps, y=y, mean=mean, rstd=rstd)
+            if attach:
+                y._mx, q = (q, y._version), None
+        else:
+            N.layernorm_fwd(R, C, x, _rows(C), gamma, beta, eps, y, _rows(C), mean, rstd)
+        return (_Act(y, q),) + self.keep(mean, rstd)  # the statistics are the backward's
+
+    def attn(self, P, T, heads, qkv, key_bias, drop=None, Tq=None):
+        """Flash attention over packed Q|K|V [P * T][3H] -> (O handle for the `o` GEMM, LSE
+        [P][heads][T], the dropout keep mask as bits (1 bit per score, read back by the backward;
+        None outside training)). Tq < T: the first Tq query rows of every sequence only, O [P * Tq][H]
+        (mmseq_attn_fwd_rows draws the attention-probability mask by the full-size index)."""
+        H = qkv.shape[-1] // 3
+        scale = 1.0 / math.sqrt(H // heads)
+        lse = torch.empty(P, heads, T, device=qkv.device)
+        kbits = N.attn_keep_bits(P, T, heads, qkv.device) if drop is not None and self.save else None
+        if "o" in self.emit:
+            if self.save:
+                o = torch.empty(P * T, H, device=qkv.device, dtype=qkv.dtype)
+                q = N.attn_fwd_mxfp8_dual(P, T, heads, qkv, 3 * H, 0, H, 2 * H, key_bias, scale, o, H,
+                                          lse, drop=drop, keep_bits=kbits)
+                return _Act(o, q), lse, kbits
+            return _Act(q=N.attn_fwd_mxfp8(P, T, heads, qkv, 3 * H, 0, H, 2 * H, key_bias, scale,
+                                           lse)), lse, kbits
+        Tq = T if Tq is None else Tq
+        o = torch.empty(P * Tq, H, device=qkv.device, dtype=qkv.dtype)
+        if Tq < T:
+            N.attn_fwd_rows(P, T, Tq, heads, qkv, key_bias, scale, o, lse, drop=drop, keep_bits=kbits)
+        else:
+            N.attn_fwd(P, T, heads, qkv, 3 * H, 0, H, 2 * H, key_bias, scale, o, H, lse, drop=drop,
+                       keep_bits=kbits)
+        return _Act(o), lse, kbits
+
+    # -- backward ---------------------------------------------------------------------------------
+    def dgrad(self, g, WT, resid=None, act=0, dact=None, q8=False):
+        """dx = g W (+ resid) or (g W) * act'(dact), WT the transposed shadow [in][out] -> handle.
+        q8: dx feeds the next dgrad directly, so an fp8 dgrad's epilogue writes its MX-fp8 copy too."""
+        if not self.f8dg:
+            return _Act(_dgrad(g.t, WT, resid=resid, act=act, dact=dact))
+        out = torch.empty(g.rows, WT.shape[0], device=g.t.device, dtype=g.t.dtype)
+        return _Act(out, N.gemm_mxfp8_ex(self._q(g), _fp8_weight(self.st, WT), out, act=act, dact=dact,
+                                         resid=resid, q8=q8))
+
+    def ln_bwd(self, dy, x, mean, rstd, gamma, dx, dres, dgamma, dbeta, dsum, dx_rows=None,
+               dx_drop=None, drop_dx=None, dx_drop_rows=None, dsum_with_dres=False):
+        """Backward of a LayerNorm whose gradient (dx_drop: dx through the dropout mask drop_dx, else
+        dx) is the output gradient of a Linear with bias gradient `dsum` -> (its handle, the bias
+        gradient left to that Linear's weight-gradient GEMM). bf16 / fp32: the LN backward sums the
+        bias gradient itself (mmseq_layernorm_bwd_ex), so the weight gradient runs without its
+        fused bias pass (None). fp8 dgrad: it writes the dgrad's MX-fp8 operand instead, and the
+        bias sum stays fused into the weight-gradient GEMM. dsum_with_dres: _native.layernorm_bwd."""
+        R, C = x.shape
+        g = dx_drop if dx_drop is not None else dx
+        if self.f8dg:
+            return _Act(g, N.layernorm_bwd_mxfp8(R, C, dy, _rows(C), x, _rows(C), mean, rstd, gamma, dx,
+                                                 _rows(C), dres, _rows(C), dgamma, dbeta,
+                                                 dx_drop=dx_drop, drop_dx=drop_dx)), dsum
+        N.layernorm_bwd(R, C, dy, _rows(C), x, _rows(C), mean, rstd, gamma, dx,
+                        dx_rows if dx_rows is not None else _rows(C), dres, _rows(C), dgamma, dbeta,
+                        dx_drop=dx_drop, drop_dx=drop_dx,
+                        dx_drop_rows=dx_drop_rows, dsum=dsum, dsum_with_dres=dsum_with_dres)
+        return _Act(g), None
+
+    def attn_bwd(self, P, T, heads, qkv, key_bias, o, do, lse, drop=None, keep_bits=None, Tq=None):
+        """-> handle of dQ|dK|dV [P * T][3H] (fp8 dgrad: also in MX-fp8, the QKV dgrad's operand).
+        Tq < T (attn's): dQ = 0 on the rows past Tq; dK / dV over every key row."""
+        H = qkv.shape[-1] // 3
+        scale = 1.0 / math.sqrt(H // heads)
+        dqkv = torch.empty_like(qkv)
+        delta = torch.empty(P, heads, T, device=qkv.device)
+        if self.f8dg:
+            return _Act(dqkv, N.attn_bwd_mxfp8(P, T, heads, qkv, key_bias, scale, o, do, lse, delta, dqkv,
+                                               drop=drop, keep_bits=keep_bits))
+        if Tq is not None and Tq < T:
+            N.attn_bwd_rows(P, T, Tq, heads, qkv, key_bias, scale, o, do, lse, delta, dqkv, drop=drop,
+                            keep_bits=keep_bits)
+        else:
+            N.attn_bwd(P, T, heads, qkv, 3 * H, 0, H, 2 * H, key_bias, scale, o, H, do, H, lse, delta,
+                       dqkv, 3 * H, drop=drop, keep_bits=keep_bits)
+        return _Act(dqkv)
+
+    def bwd_done(self):
+        _fp8_bwd_done(self.f8dg)
 
 
-def _dgrad8(dy, st, WT, resid=None, act=0, dact=None, dyq=None, q8=False):
-    """dx = dy W (+ resid) or (dy W) * act'(dact) on the fp8 MFMA: dy's MX-fp8 copy from its producer
-    (dyq) or quantised here, the transposed weight shadow WT [in][out] once per store version
-    (config 5, dgrad=True). q8: also return the output's MX-fp8 copy (the next dgrad's operand)."""
-    R = dy.numel() // dy.shape[-1]
-    out = torch.empty(R, WT.shape[0], device=dy.device, dtype=dy.dtype)
-    q = N.gemm_mxfp8_ex(dyq if dyq is not None else N.quant_mxfp8(dy.view(R, -1)),
-                        _fp8_weight(st, WT), out, act=act, dact=dact, resid=resid, q8=q8)
-    return (out, q) if q8 else out
+def _engine(kind, st, x, Ws, save, drops=(None, None, None), Tq=None):
+    """The engine for one forward of a layer of `kind` ("vit" / "joint") with input x [R][K] and
+    weights Ws = (qkv, o, fc1, fc2), [out][in]: every eligibility rule lives here.
+
+    - bf16 / fp32 (no site on the fp8 MFMA): fp8_forward() off, an fp32 model, a layer on its text
+      rows (Tq: ~1/3 of the rows; the other layers keep the fp8 GEMMs), or shapes fp8 does not take.
+    - fp8 training (save, fp8_forward(training=True)): all four GEMMs in the 256 x 256 8-phase
+      MX-fp8 form (K and widths multiples of 256), a hidden width the fused MX-fp8 LayerNorm takes
+      (<= 1024), >= 256 rows; dropout masks as in bf16 training.
+    - mixed placement (eval, fp8_forward(sites=...) with some of the kind's sites on): those sites
+      from unfused blocks, no shape guard (a shape the fp8 GEMM cannot take raises). A kind with
+      all four sites on is fused, one with none bf16.
+    - fused fp8 eval: QKV and O with K a multiple of 256 (attention and hidden dropout off);
+      the FFN with K and the intermediate width multiples of 256, else (multiples of 128) FC1 on
+      the bf16 MFMA with an MX-fp8 epilogue and FC2 in fp8; the output dropout is off in
+      inference. Without fp8 QKV / O the FFN alone still takes whichever of the two forms fits, fed
+      by a bf16 LayerNorm."""
+    plain = _Engine(st, save=save)
+    if not _FP8["on"] or x.dtype != torch.bfloat16 or Tq is not None:
+        return plain
+    K, I = Ws[2].shape[1], Ws[2].shape[0]
+    wide = K % 256 == 0 and K <= 1024 and x.is_contiguous()
+    if save:
+        if _FP8["train"] and wide and x.shape[0] >= 256 and all(
+                W.shape[0] % 256 == 0 and W.shape[1] % 256 == 0 for W in Ws):
+            return _Engine(st, FP8_SITES, FP8_SITES, True, _FP8["dgrad"])
+        return plain
+    sel = _FP8["sites"]
+    on = [s for s in FP8_SITES if sel is None or s in sel or f"{kind}.{s}" in sel]
+    if 0 < len(on) < len(FP8_SITES):
+        return _Engine(st, on) if drops == (None, None, None) else plain
+    d_att, d_o, d_out = drops
+    f8 = set()
+    if on and wide and Ws[0].shape[0] % 256 == 0 and d_att is None and d_o is None:
+        assert d_out is None, "eval fp8 path: the output dropout is off in inference"
+        f8 = {"qkv", "o"}
+    if on and d_out is None and K % 128 == 0 and I % 128 == 0:
+        f8.add("fc2")
+        if wide and I % 256 == 0 and Ws[3].shape[0] % 256 == 0:
+            f8.add("fc1")
+    # without fp8 QKV / O the LayerNorm in front of FC1 stays bf16 and FC1 quantises its input
+    return _Engine(st, f8, f8 if "qkv" in f8 else f8 - {"fc1"})
 
 
 def _dgrad(dy, WT, resid=None, act=0, dact=None, out=None):
@@ -297,10 +391,6 @@ class LayerRefs:
 # the last joint layer on the text rows only (BertLayerFn Tq); off (or MMSEQ_ROWS=0 in the
 # environment, for A/B runs): every layer over all T rows
 ROWS = {"on": os.environ.get("MMSEQ_ROWS", "1") != "0"}
-# the bias gradients of the two Linears whose output gradient a LayerNorm backward writes
-# (BertSelfOutput / BertOutput dense, the ViT out_proj) summed by that LN backward
-# (mmseq_layernorm_bwd_ex) instead of fused into their weight-gradient GEMMs; MMSEQ_LN_BIAS=0: fused
-LN_BIAS = {"on": os.environ.get("MMSEQ_LN_BIAS", "1") != "0"}
 
 
 # ================================================================================================
@@ -322,269 +412,83 @@ class BertLayerFn(torch.autograd.Function):
         pre-activation). Tq (< T, rows_ok): only the first Tq rows of every sequence leave the
         layer (the last joint layer, whose visual rows _split_with_none discards,
         lxrt/modeling.py:611-618): QKV over all T rows (the keys and values), everything after
-        the attention on the P * Tq text rows; returns [P * Tq][H]."""
+        the attention on the P * Tq text rows; returns [P * Tq][H]. Every kept row equals the
+        full-size layer's; in train mode the attention-probability mask too (mmseq_attn_fwd_rows
+        draws it by the full-size index), while the two hidden-dropout sites after the attention
+        (:437, :491) index their masks by the compacted [P * Tq][H] layout: an equally distributed
+        draw, regenerated identically by this layer's backward."""
         st = L.store
         H = x.shape[-1]
         d_att, d_o, d_out = drops
-        # the previous layer's MX-fp8 copy of x (fp8_forward): detached here so that saving x for
-        # backward does not keep it alive; the paths that do not read it drop it
-        xmx = x.__dict__.pop("_mx", None)
-        Wqkv = st.packed(L.qkv_w, "w")
-        bqkv = st.packed(L.qkv_b, "f32").view(-1)
-        if Tq is not None and Tq < T:
-            return BertLayerFn._forward_rows(ctx, x, key_bias, L, P, T, Tq, heads, eps, drops, save,
-                                             Wqkv, bqkv)
-        if save and _f8_train(x, Wqkv, st.w(L.o_w), st.w(L.i_w), st.w(L.out_w)):
-            return BertLayerFn._forward_f8_train(ctx, x, key_bias, L, P, T, heads, eps, drops, Wqkv, bqkv,
-                                                 xmx)
-        if not save and _mixed("joint") and x.dtype == torch.bfloat16 and drops == (None, None, None):
-            return BertLayerFn._forward_mixed(x, key_bias, L, P, T, heads, eps, Wqkv, bqkv)
-        f8 = not save and _f8(x, Wqkv, "joint") and d_att is None and d_o is None
-        qkv = _lin8(st, x, Wqkv, bias=bqkv, xq=_mx(x, xmx)) if f8 else _linear(x, Wqkv, bias=bqkv)
-        del xmx
-        lse = torch.empty(P, heads, T, device=x.device)
-        if f8:  # eval: attention writes the output projection's MX-fp8 operand directly
-            oq = N.attn_fwd_mxfp8(P, T, heads, qkv, 3 * H, 0, H, 2 * H, key_bias,
-                                  1.0 / math.sqrt(H // heads), lse)
-            s1 = _lin8(st, None, st.w(L.o_w), bias=st.f32(L.o_b), resid=x, xq=oq)
-            return BertLayerFn._ffn_f8(st, L, x, s1, eps, d_out)
-        o = torch.empty_like(x)
-        # the forward's dropout keep mask as bits (1 bit per score; read back by the backward)
-        kbits = (N.attn_keep_bits(P, T, heads, x.device) if d_att is not None and save else None)
-        N.attn_fwd(P, T, heads, qkv, 3 * H, 0, H, 2 * H, key_bias, 1.0 / math.sqrt(H // heads), o,
-                   H, lse, drop=d_att, keep_bits=kbits)
-        s1 = _linear(o, st.w(L.o_w), bias=st.f32(L.o_b), resid=x, drop=d_o)
-        h1 = torch.empty_like(x)
-        m1 = torch.empty(s1.shape[0], device=x.device)
-        r1 = torch.empty_like(m1)
-        N.layernorm_fwd(s1.shape[0], H, s1, _rows(H), st.f32(L.ln1_w), st.f32(L.ln1_b), eps, h1,
-                        _rows(H), m1, r1)
+        Tq = T if Tq is None else Tq
+        Ws = (st.packed(L.qkv_w, "w"), st.w(L.o_w), st.w(L.i_w), st.w(L.out_w))
+        eng = _engine("joint", st, x, Ws, save, drops, Tq if Tq < T else None)
+        xa = _act_in(x)
+        qkv = eng.linear("qkv", xa, Ws[0], st.packed(L.qkv_b, "f32").view(-1)).t
+        del xa
+        o, lse, kbits = eng.attn(P, T, heads, qkv, key_bias, d_att, Tq)
+        xr = x.view(P, T, H)[:, :Tq].reshape(P * Tq, H)  # the residual: x, or (Tq < T) its text rows
+        s1 = eng.linear("o", o, Ws[1], st.f32(L.o_b), resid=xr, drop=d_o).t
+        del xr
+        o = eng.keep(o)
+        h1, m1, r1 = eng.ln(s1, st.f32(L.ln1_w), st.f32(L.ln1_b), eps, "fc1", keep=True)
+        g, z = eng.linear("fc1", h1, Ws[2], st.f32(L.i_b), act=GELU, to="fc2", pre=True)
+        h1 = h1.t
+        s2 = eng.linear("fc2", g, Ws[3], st.f32(L.out_b), resid=h1, drop=d_out).t
+        gact = eng.keep(g)
+        del g
+        y, m2, r2 = eng.ln(s2, st.f32(L.ln2_w), st.f32(L.ln2_b), eps, "qkv", keep=True, attach=True)
         if save:
-            z = torch.empty(x.shape[0], st.w(L.i_w).shape[0], device=x.device, dtype=x.dtype)
-            gact = _linear(h1, st.w(L.i_w), bias=st.f32(L.i_b), act=GELU, aux=z)
-            s2 = _linear(gact, st.w(L.out_w), bias=st.f32(L.out_b), resid=h1, drop=d_out)
-        elif d_out is None:
-            s2 = _mlp_fwd(st, h1, st.w(L.i_w), st.f32(L.i_b), GELU, st.w(L.out_w),
-                          st.f32(L.out_b), h1, _linear, kind="joint")
-        else:
-            gact = _linear(h1, st.w(L.i_w), bias=st.f32(L.i_b), act=GELU)
-            s2 = _linear(gact, st.w(L.out_w), bias=st.f32(L.out_b), resid=h1, drop=d_out)
-        y = torch.empty_like(x)
-        m2 = torch.empty_like(m1)
-        r2 = torch.empty_like(m1)
-        N.layernorm_fwd(s2.shape[0], H, s2, _rows(H), st.f32(L.ln2_w), st.f32(L.ln2_b), eps, y,
-                        _rows(H), m2, r2)
-        if not save:
-            return y
-        ctx.save_for_backward(x, key_bias, qkv, o, lse, s1, m1, r1, h1, z, gact, s2, m2, r2)
-        ctx.meta = (L, P, T, heads, drops)
-        ctx.kbits = kbits
-        return y
-
-    @staticmethod
-    def _forward_mixed(x, key_bias, L, P, T, heads, eps, Wqkv, bqkv):
-        """Eval forward under fp8_forward(sites=...): each of the four GEMMs on the fp8 or the bf16
-        MFMA by its site (_lin_site); attention and LayerNorms as in bf16."""
-        st = L.store
-        H = x.shape[-1]
-        qkv = _lin_site("joint", "qkv", st, x, Wqkv, bias=bqkv)
-        lse = torch.empty(P, heads, T, device=x.device)
-        o = torch.empty_like(x)
-        N.attn_fwd(P, T, heads, qkv, 3 * H, 0, H, 2 * H, key_bias, 1.0 / math.sqrt(H // heads), o, H, lse)
-        s1 = _lin_site("joint", "o", st, o, st.w(L.o_w), bias=st.f32(L.o_b), resid=x)
-        h1 = torch.empty_like(x)
-        m = torch.empty(s1.shape[0], device=x.device)
-        r = torch.empty_like(m)
-        N.layernorm_fwd(s1.shape[0], H, s1, _rows(H), st.f32(L.ln1_w), st.f32(L.ln1_b), eps, h1, _rows(H), m, r)
-        g = _lin_site("joint", "fc1", st, h1, st.w(L.i_w), bias=st.f32(L.i_b), act=GELU)
-        s2 = _lin_site("joint", "fc2", st, g, st.w(L.out_w), bias=st.f32(L.out_b), resid=h1)
-        y = torch.empty_like(x)
-        N.layernorm_fwd(s2.shape[0], H, s2, _rows(H), st.f32(L.ln2_w), st.f32(L.ln2_b), eps, y, _rows(H), m, r)
-        return y
-
-    @staticmethod
-    def _forward_rows(ctx, x, key_bias, L, P, T, Tq, heads, eps, drops, save, Wqkv, bqkv):
-        """forward() with Tq < T. Every kept row equals the full-size layer's; in train mode the
-        attention-probability mask too (mmseq_attn_fwd_rows draws it by the full-size index), while
-        the two hidden-dropout sites after the attention (:437, :491) index their masks by the
-        compacted [P * Tq][H] layout: an equally distributed draw, regenerated identically by
-        this layer's backward."""
-        st = L.store
-        H = x.shape[-1]
-        d_att, d_o, d_out = drops
-        qkv = _linear(x, Wqkv, bias=bqkv)
-        lse = torch.empty(P, heads, T, device=x.device)
-        o = torch.empty(P * Tq, H, device=x.device, dtype=x.dtype)
-        kbits = N.attn_keep_bits(P, T, heads, x.device) if d_att is not None and save else None
-        N.attn_fwd_rows(P, T, Tq, heads, qkv, key_bias, 1.0 / math.sqrt(H // heads), o, lse,
-                        drop=d_att, keep_bits=kbits)
-        xt = x.view(P, T, H)[:, :Tq].reshape(P * Tq, H)  # the residual's text rows
-        s1 = _linear(o, st.w(L.o_w), bias=st.f32(L.o_b), resid=xt, drop=d_o)
-        del xt
-        R = P * Tq
-        h1 = torch.empty_like(s1)
-        m1 = torch.empty(R, device=x.device)
-        r1 = torch.empty_like(m1)
-        N.layernorm_fwd(R, H, s1, _rows(H), st.f32(L.ln1_w), st.f32(L.ln1_b), eps, h1, _rows(H), m1, r1)
-        z = torch.empty(R, st.w(L.i_w).shape[0], device=x.device, dtype=x.dtype) if save else None
-        gact = _linear(h1, st.w(L.i_w), bias=st.f32(L.i_b), act=GELU, aux=z)
-        s2 = _linear(gact, st.w(L.out_w), bias=st.f32(L.out_b), resid=h1, drop=d_out)
-        y = torch.empty_like(s1)
-        m2 = torch.empty_like(m1)
-        r2 = torch.empty_like(m1)
-        N.layernorm_fwd(R, H, s2, _rows(H), st.f32(L.ln2_w), st.f32(L.ln2_b), eps, y, _rows(H), m2, r2)
-        if not save:
-            return y
-        ctx.save_for_backward(x, key_bias, qkv, o, lse, s1, m1, r1, h1, z, gact, s2, m2, r2)
-        ctx.meta = (L, P, T, heads, drops)
-        ctx.kbits = kbits
-        ctx.Tq = Tq
-        return y
-
-    @staticmethod
-    def _forward_f8_train(ctx, x, key_bias, L, P, T, heads, eps, drops, Wqkv, bqkv, xmx=None):
-        """Training forward with QKV / O / FC1 / FC2 on the fp8 MFMA: the bf16 tensors the (bf16)
-        backward reads are written by the same producers that write the next GEMM's MX-fp8
-        operand (attention O, LayerNorm h1 / y, FC1's GELU output + pre-activation)."""
-        st = L.store
-        H = x.shape[-1]
-        R = x.shape[0]
-        d_att, d_o, d_out = drops
-        qkv = torch.empty(R, 3 * H, device=x.device, dtype=x.dtype)
-        N.gemm_mxfp8_ex(_mx(x, xmx), _fp8_weight(st, Wqkv), qkv, bias=bqkv)
-        del xmx
-        lse = torch.empty(P, heads, T, device=x.device)
-        kbits = N.attn_keep_bits(P, T, heads, x.device) if d_att is not None else None
-        o = torch.empty_like(x)
-        oq = N.attn_fwd_mxfp8_dual(P, T, heads, qkv, 3 * H, 0, H, 2 * H, key_bias,
-                                   1.0 / math.sqrt(H // heads), o, H, lse, drop=d_att, keep_bits=kbits)
-        s1 = torch.empty_like(x)
-        N.gemm_mxfp8_ex(oq, _fp8_weight(st, st.w(L.o_w)), s1, bias=st.f32(L.o_b), resid=x, drop=d_o)
-        del oq
-        h1 = torch.empty_like(x)
-        m1 = torch.empty(R, device=x.device)
-        r1 = torch.empty_like(m1)
-        h1q = _ln8(s1, st.f32(L.ln1_w), st.f32(L.ln1_b), eps, mean=m1, rstd=r1, y=h1)
-        I = st.w(L.i_w).shape[0]
-        z = torch.empty(R, I, device=x.device, dtype=x.dtype)
-        gact = torch.empty_like(z)
-        gq = N.gemm_mxfp8_ex(h1q, _fp8_weight(st, st.w(L.i_w)), gact, bias=st.f32(L.i_b), act=GELU,
-                             aux=z, q8=True)
-        del h1q
-        s2 = torch.empty_like(x)
-        N.gemm_mxfp8_ex(gq, _fp8_weight(st, st.w(L.out_w)), s2, bias=st.f32(L.out_b), resid=h1,
-                        drop=d_out)
-        del gq
-        y = torch.empty_like(x)
-        m2 = torch.empty_like(m1)
-        r2 = torch.empty_like(m1)
-        _ln8(s2, st.f32(L.ln2_w), st.f32(L.ln2_b), eps, y=y, mean=m2, rstd=r2, attach=True)
-        ctx.save_for_backward(x, key_bias, qkv, o, lse, s1, m1, r1, h1, z, gact, s2, m2, r2)
-        ctx.meta = (L, P, T, heads, drops)
-        ctx.kbits = kbits
-        ctx.f8dg = _FP8["dgrad"]
-        return y
-
-    @staticmethod
-    def _ffn_f8(st, L, x, s1, eps, d_out):
-        """Eval fp8 tail of the layer: LN1 (bf16 out for the residual + MX-fp8 for FC1), FC1 ->
-        FC2 on the fp8 MFMA, LN2 (bf16 out + MX-fp8 copy for the next layer's QKV)."""
-        h1 = torch.empty_like(x)
-        m = torch.empty(s1.shape[0], device=x.device)
-        r = torch.empty_like(m)
-        if d_out is None and _f8(h1, st.w(L.i_w)) and st.w(L.out_w).shape[0] % 256 == 0:
-            h1q = _ln8(s1, st.f32(L.ln1_w), st.f32(L.ln1_b), eps, y=h1, mean=m, rstd=r)
-            s2 = _mlp_fwd(st, h1, st.w(L.i_w), st.f32(L.i_b), GELU, st.w(L.out_w), st.f32(L.out_b),
-                          h1, _linear, xq=h1q)
-        else:
-            assert d_out is None, "eval fp8 path: the output dropout is off in inference"
-            H = x.shape[-1]
-            N.layernorm_fwd(s1.shape[0], H, s1, _rows(H), st.f32(L.ln1_w), st.f32(L.ln1_b), eps,
-                            h1, _rows(H), m, r)
-            s2 = _mlp_fwd(st, h1, st.w(L.i_w), st.f32(L.i_b), GELU, st.w(L.out_w), st.f32(L.out_b),
-                          h1, _linear)
-        y = torch.empty_like(x)
-        _ln8(s2, st.f32(L.ln2_w), st.f32(L.ln2_b), eps, y=y, mean=m, rstd=r, attach=True)
-        return y
+            ctx.save_for_backward(x, key_bias, qkv, o, lse, s1, m1, r1, h1, z, gact, s2, m2, r2)
+            ctx.meta = (L, P, T, Tq, heads, drops)
+            ctx.kbits = kbits
+            ctx.eng = eng
+        return y.t
 
     @staticmethod
     def backward(ctx, dy):
         x, key_bias, qkv, o, lse, s1, m1, r1, h1, z, gact, s2, m2, r2 = ctx.saved_tensors
-        L, P, T, heads, (d_att, d_o, d_out) = ctx.meta
-        Tq = getattr(ctx, "Tq", T)  # < T: the rows after the attention are the P * Tq text rows
+        L, P, T, Tq, heads, (d_att, d_o, d_out) = ctx.meta  # Tq < T: dy is over the P * Tq text rows
+        eng = ctx.eng
         st = L.store
         st.grad_begin()
         H = x.shape[-1]
         dy = dy.contiguous()
-        R = dy.shape[0]
         # LN backward also emits the dense-branch gradient through the dropout mask (ds2d) while
         # the residual branch keeps the unmasked one (ds2)
         ds2 = torch.empty_like(dy)
-        ds2d = torch.empty_like(dy) if d_out is not None else ds2
-        f8 = getattr(ctx, "f8dg", False)  # fp8 dgrad: the LN backwards also write the MX-fp8 operand
-        lnb = N.layernorm_bwd_mxfp8 if f8 else N.layernorm_bwd
-        # bf16 / fp32: the LN backward also sums the gradient it writes for FC2 (BertOutput.dense's
-        # bias gradient), so the FC2 weight gradient runs without its fused bias pass
-        lnsum = LN_BIAS["on"] and not f8
-        bkw = {"dsum": st.g(L.out_b)} if lnsum else {}
-        ds2q = lnb(R, H, dy, _rows(H), s2, _rows(H), m2, r2, st.f32(L.ln2_w), ds2, _rows(H),
-                   None, _rows(H), st.g(L.ln2_w), st.g(L.ln2_b),
-                   dx_drop=ds2d if d_out is not None else None, drop_dx=d_out, **bkw)
-        _wgrad(ds2d, gact, st.g(L.out_w), None if lnsum else st.g(L.out_b))
-        dzq = None  # fp8 dgrad: FC2's dgrad epilogue writes FC1's dgrad operand in MX-fp8 as well
-        if f8:
-            dz, dzq = _dgrad8(ds2d, st, st.wt(L.out_w), act=GELU, dact=z, dyq=ds2q, q8=True)
-        else:
-            dz = _dgrad(ds2d, st.wt(L.out_w), act=GELU, dact=z)
+        ds2d = torch.empty_like(dy) if d_out is not None else None
+        g2, gb = eng.ln_bwd(dy, s2, m2, r2, st.f32(L.ln2_w), ds2, None, st.g(L.ln2_w), st.g(L.ln2_b),
+                            st.g(L.out_b), dx_drop=ds2d, drop_dx=d_out)
         del ds2d
-        _wgrad(dz, h1, st.g(L.i_w), st.g(L.i_b))
-        dh1 = _dgrad8(dz, st, st.wt(L.i_w), resid=ds2, dyq=dzq) if f8 else _dgrad(dz, st.wt(L.i_w), resid=ds2)
-        del dz, dzq
+        _wgrad(g2.t, gact, st.g(L.out_w), gb)
+        dz = eng.dgrad(g2, st.wt(L.out_w), act=GELU, dact=z, q8=True)
+        del g2
+        _wgrad(dz.t, h1, st.g(L.i_w), st.g(L.i_b))
+        dh1 = eng.dgrad(dz, st.wt(L.i_w), resid=ds2).t
+        del dz
         if Tq < T:  # the residual branch's gradient goes straight into its rows of the full-size
             # [P * T] buffer the QKV dgrad adds in fp32 (zero on the visual rows: bit-identical to
             # the full-size layer); the dense branch's (masked) copy stays compact
             ds1 = torch.empty(P * T, H, device=dy.device, dtype=dy.dtype)
             ds1.view(P, T, H)[:, Tq:].zero_()
-            ds1d = torch.empty_like(dy)
-            N.layernorm_bwd(R, H, dh1, _rows(H), s1, _rows(H), m1, r1, st.f32(L.ln1_w), ds1,
-                            N.rows(H, T * H, Tq), None, _rows(H), st.g(L.ln1_w), st.g(L.ln1_b),
-                            dx_drop=ds1d, drop_dx=d_o, dx_drop_rows=_rows(H),
-                            dsum=st.g(L.o_b) if lnsum else None)
-            ds1q = None
+            g1, gb = eng.ln_bwd(dh1, s1, m1, r1, st.f32(L.ln1_w), ds1, None, st.g(L.ln1_w),
+                                st.g(L.ln1_b), st.g(L.o_b), dx_rows=N.rows(H, T * H, Tq),
+                                dx_drop=torch.empty_like(dy), drop_dx=d_o, dx_drop_rows=_rows(H))
         else:
             ds1 = torch.empty_like(dy)
-            ds1d = torch.empty_like(dy) if d_o is not None else ds1
-            ds1q = lnb(R, H, dh1, _rows(H), s1, _rows(H), m1, r1, st.f32(L.ln1_w), ds1, _rows(H),
-                       None, _rows(H), st.g(L.ln1_w), st.g(L.ln1_b),
-                       dx_drop=ds1d if d_o is not None else None, drop_dx=d_o,
-                       **({"dsum": st.g(L.o_b)} if lnsum else {}))
-        # the attention output projection's bias gradient: summed by the LN backward above, or
-        # (fp8 dgrad) fused into its weight-gradient GEMM
-        _wgrad(ds1d, o, st.g(L.o_w), None if lnsum else st.g(L.o_b))
-        do = _dgrad8(ds1d, st, st.wt(L.o_w), dyq=ds1q) if f8 else _dgrad(ds1d, st.wt(L.o_w))
-        del ds1d
-        dqkv = torch.empty_like(qkv)
-        delta = torch.empty(P, heads, T, device=x.device)
-        if Tq < T:  # dQ = 0 on the rows past Tq; dK / dV over every key row
-            N.attn_bwd_rows(P, T, Tq, heads, qkv, key_bias, 1.0 / math.sqrt(H // heads), o, do, lse,
-                            delta, dqkv, drop=d_att, keep_bits=ctx.kbits)
-            ctx.kbits = None
-            _wgrad(dqkv, x, st.packed(L.qkv_w, "g"), st.packed(L.qkv_b, "g").view(-1))
-            st.grad_ready(L.span)
-            dx = _dgrad(dqkv, st.wt(L.qkv_w[0]), resid=ds1)
-            return dx, None, None, None, None, None, None, None, None, None, None
-        if f8:  # dQ|dK|dV also in MX-fp8: the QKV dgrad's operand
-            dqkvq = N.attn_bwd_mxfp8(P, T, heads, qkv, key_bias, 1.0 / math.sqrt(H // heads), o, do,
-                                     lse, delta, dqkv, drop=d_att, keep_bits=ctx.kbits)
-        else:
-            N.attn_bwd(P, T, heads, qkv, 3 * H, 0, H, 2 * H, key_bias, 1.0 / math.sqrt(H // heads), o,
-                       H, do, H, lse, delta, dqkv, 3 * H, drop=d_att, keep_bits=ctx.kbits)
+            g1, gb = eng.ln_bwd(dh1, s1, m1, r1, st.f32(L.ln1_w), ds1, None, st.g(L.ln1_w),
+                                st.g(L.ln1_b), st.g(L.o_b),
+                                dx_drop=torch.empty_like(dy) if d_o is not None else None, drop_dx=d_o)
+        _wgrad(g1.t, o, st.g(L.o_w), gb)
+        do = eng.dgrad(g1, st.wt(L.o_w)).t
+        del g1
+        dqkv = eng.attn_bwd(P, T, heads, qkv, key_bias, o, do, lse, d_att, ctx.kbits, Tq)
         ctx.kbits = None
-        _wgrad(dqkv, x, st.packed(L.qkv_w, "g"), st.packed(L.qkv_b, "g").view(-1))
+        _wgrad(dqkv.t, x, st.packed(L.qkv_w, "g"), st.packed(L.qkv_b, "g").view(-1))
         st.grad_ready(L.span)
-        dx = _dgrad8(dqkv, st, st.wt(L.qkv_w[0]), resid=ds1, dyq=dqkvq) if f8 else \
-            _dgrad(dqkv, st.wt(L.qkv_w[0]), resid=ds1)
-        _fp8_bwd_done(f8)
+        dx = eng.dgrad(dqkv, st.wt(L.qkv_w[0]), resid=ds1).t
+        eng.bwd_done()
         return dx, None, None, None, None, None, None, None, None, None, None
 
 
@@ -594,144 +498,59 @@ class BertLayerFn(torch.autograd.Function):
 class VitBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, anchor, L, P, T, heads, eps, save=True):
+        """in_proj / out_proj / c_fc / c_proj are the sites qkv / o / fc1 / fc2. The LayerNorm
+        outputs are only GEMM operands (pre-LN): in eval they may leave in MX-fp8 alone; a training
+        forward keeps the bf16 tensors the weight gradients read."""
         st = L.store
-        W = h.shape[-1]
-        R = h.shape[0]
-        m1 = torch.empty(R, device=h.device)
-        r1 = torch.empty_like(m1)
-        if save and _f8_train(h, st.w(L.in_w), st.w(L.out_w), st.w(L.fc_w), st.w(L.proj_w)):
-            return VitBlockFn._forward_f8_train(ctx, h, L, P, T, heads, eps, m1, r1)
-        if not save and _mixed("vit") and h.dtype == torch.bfloat16:  # fp8_forward(sites=...)
-            hn = torch.empty_like(h)
-            N.layernorm_fwd(R, W, h, _rows(W), st.f32(L.ln1_w), st.f32(L.ln1_b), eps, hn, _rows(W), m1, r1)
-            qkv = _lin_site("vit", "qkv", st, hn, st.w(L.in_w), bias=st.f32(L.in_b))
-            lse = torch.empty(P, heads, T, device=h.device)
-            o = torch.empty_like(h)
-            N.attn_fwd(P, T, heads, qkv, 3 * W, 0, W, 2 * W, None, 1.0 / math.sqrt(W // heads), o, W, lse)
-            x1 = _lin_site("vit", "o", st, o, st.w(L.out_w), bias=st.f32(L.out_b), resid=h)
-            N.layernorm_fwd(R, W, x1, _rows(W), st.f32(L.ln2_w), st.f32(L.ln2_b), eps, hn, _rows(W), m1, r1)
-            g = _lin_site("vit", "fc1", st, hn, st.w(L.fc_w), bias=st.f32(L.fc_b), act=QGELU)
-            return _lin_site("vit", "fc2", st, g, st.w(L.proj_w), bias=st.f32(L.proj_b), resid=x1)
-        f8 = not save and _f8(h, st.w(L.in_w), "vit") and _f8(h, st.w(L.fc_w), "vit")
-        if f8:  # eval, fp8 GEMMs: the LayerNorm outputs are only GEMM operands -> MX-fp8 only
-            hq = _ln8(h, st.f32(L.ln1_w), st.f32(L.ln1_b), eps, mean=m1, rstd=r1)
-            qkv = _lin8(st, None, st.w(L.in_w), bias=st.f32(L.in_b), xq=hq)
-        else:
-            hn = torch.empty_like(h)
-            N.layernorm_fwd(R, W, h, _rows(W), st.f32(L.ln1_w), st.f32(L.ln1_b), eps, hn, _rows(W),
-                            m1, r1)
-            qkv = _linear(hn, st.w(L.in_w), bias=st.f32(L.in_b))
-        lse = torch.empty(P, heads, T, device=h.device)
-        if f8:
-            oq = N.attn_fwd_mxfp8(P, T, heads, qkv, 3 * W, 0, W, 2 * W, None,
-                                  1.0 / math.sqrt(W // heads), lse)
-            x1 = _lin8(st, None, st.w(L.out_w), bias=st.f32(L.out_b), resid=h, xq=oq)
-        else:
-            o = torch.empty_like(h)
-            N.attn_fwd(P, T, heads, qkv, 3 * W, 0, W, 2 * W, None, 1.0 / math.sqrt(W // heads), o,
-                       W, lse)
-            x1 = _linear(o, st.w(L.out_w), bias=st.f32(L.out_b), resid=h)
-        m2 = torch.empty_like(m1)
-        r2 = torch.empty_like(m1)
-        if f8:
-            hq2 = _ln8(x1, st.f32(L.ln2_w), st.f32(L.ln2_b), eps, mean=m2, rstd=r2)
-            return _mlp_fwd(st, None, st.w(L.fc_w), st.f32(L.fc_b), QGELU, st.w(L.proj_w),
-                            st.f32(L.proj_b), x1, _linear, xq=hq2)
-        hn2 = torch.empty_like(h)
-        N.layernorm_fwd(R, W, x1, _rows(W), st.f32(L.ln2_w), st.f32(L.ln2_b), eps, hn2, _rows(W),
-                        m2, r2)
-        if not save:
-            return _mlp_fwd(st, hn2, st.w(L.fc_w), st.f32(L.fc_b), QGELU, st.w(L.proj_w),
-                            st.f32(L.proj_b), x1, _linear, kind="vit")
-        z = torch.empty(R, st.w(L.fc_w).shape[0], device=h.device, dtype=h.dtype)
-        gact = _linear(hn2, st.w(L.fc_w), bias=st.f32(L.fc_b), act=QGELU, aux=z)
-        x2 = _linear(gact, st.w(L.proj_w), bias=st.f32(L.proj_b), resid=x1)
-        ctx.save_for_backward(h, m1, r1, hn, qkv, o, lse, x1, m2, r2, hn2, z, gact)
-        ctx.meta = (L, P, T, heads)
-        return x2
-
-    @staticmethod
-    def _forward_f8_train(ctx, h, L, P, T, heads, eps, m1, r1):
-        """Training forward with in_proj / out_proj / c_fc / c_proj on the fp8 MFMA (the LayerNorms
-        write the bf16 GEMM inputs the wgrads read plus the MX-fp8 operands; c_fc writes the
-        QuickGELU output, its pre-activation and c_proj's MX-fp8 operand)."""
-        st = L.store
-        W = h.shape[-1]
-        R = h.shape[0]
-        hn = torch.empty_like(h)
-        hq = _ln8(h, st.f32(L.ln1_w), st.f32(L.ln1_b), eps, y=hn, mean=m1, rstd=r1)
-        qkv = torch.empty(R, 3 * W, device=h.device, dtype=h.dtype)
-        N.gemm_mxfp8_ex(hq, _fp8_weight(st, st.w(L.in_w)), qkv, bias=st.f32(L.in_b))
-        del hq
-        lse = torch.empty(P, heads, T, device=h.device)
-        o = torch.empty_like(h)
-        oq = N.attn_fwd_mxfp8_dual(P, T, heads, qkv, 3 * W, 0, W, 2 * W, None,
-                                   1.0 / math.sqrt(W // heads), o, W, lse)
-        x1 = torch.empty_like(h)
-        N.gemm_mxfp8_ex(oq, _fp8_weight(st, st.w(L.out_w)), x1, bias=st.f32(L.out_b), resid=h)
-        del oq
-        m2 = torch.empty_like(m1)
-        r2 = torch.empty_like(m1)
-        hn2 = torch.empty_like(h)
-        hq2 = _ln8(x1, st.f32(L.ln2_w), st.f32(L.ln2_b), eps, y=hn2, mean=m2, rstd=r2)
-        F = st.w(L.fc_w).shape[0]
-        z = torch.empty(R, F, device=h.device, dtype=h.dtype)
-        gact = torch.empty_like(z)
-        gq = N.gemm_mxfp8_ex(hq2, _fp8_weight(st, st.w(L.fc_w)), gact, bias=st.f32(L.fc_b), act=QGELU,
-                             aux=z, q8=True)
-        del hq2
-        x2 = torch.empty_like(h)
-        N.gemm_mxfp8_ex(gq, _fp8_weight(st, st.w(L.proj_w)), x2, bias=st.f32(L.proj_b), resid=x1)
-        ctx.save_for_backward(h, m1, r1, hn, qkv, o, lse, x1, m2, r2, hn2, z, gact)
-        ctx.meta = (L, P, T, heads)
-        ctx.f8dg = _FP8["dgrad"]
+        Ws = (st.w(L.in_w), st.w(L.out_w), st.w(L.fc_w), st.w(L.proj_w))
+        eng = _engine("vit", st, h, Ws, save)
+        hn, m1, r1 = eng.ln(h, st.f32(L.ln1_w), st.f32(L.ln1_b), eps, "qkv")
+        qkv = eng.linear("qkv", hn, Ws[0], st.f32(L.in_b)).t
+        hn = eng.keep(hn)
+        o, lse, _ = eng.attn(P, T, heads, qkv, None)
+        x1 = eng.linear("o", o, Ws[1], st.f32(L.out_b), resid=h).t
+        o = eng.keep(o)
+        hn2, m2, r2 = eng.ln(x1, st.f32(L.ln2_w), st.f32(L.ln2_b), eps, "fc1")
+        g, z = eng.linear("fc1", hn2, Ws[2], st.f32(L.fc_b), act=QGELU, to="fc2", pre=True)
+        hn2 = eng.keep(hn2)
+        x2 = eng.linear("fc2", g, Ws[3], st.f32(L.proj_b), resid=x1).t
+        if save:
+            ctx.save_for_backward(h, m1, r1, hn, qkv, o, lse, x1, m2, r2, hn2, z, eng.keep(g))
+            ctx.meta = (L, P, T, heads)
+            ctx.eng = eng
         return x2
 
     @staticmethod
     def backward(ctx, dx2):
         h, m1, r1, hn, qkv, o, lse, x1, m2, r2, hn2, z, gact = ctx.saved_tensors
         L, P, T, heads = ctx.meta
+        eng = ctx.eng
         st = L.store
         st.grad_begin()
         W = h.shape[-1]
         R = h.shape[0]
         dx2 = dx2.contiguous()
-        f8 = getattr(ctx, "f8dg", False)
-        dg = (lambda d, WT, **kw: _dgrad8(d, st, WT, **kw)) if f8 else _dgrad
         _wgrad(dx2, gact, st.g(L.proj_w), st.g(L.proj_b))
-        dzq = None
-        if f8:
-            dz, dzq = _dgrad8(dx2, st, st.wt(L.proj_w), act=QGELU, dact=z, q8=True)
-        else:
-            dz = _dgrad(dx2, st.wt(L.proj_w), act=QGELU, dact=z)
-        _wgrad(dz, hn2, st.g(L.fc_w), st.g(L.fc_b))
-        dhn2 = _dgrad8(dz, st, st.wt(L.fc_w), dyq=dzq) if f8 else _dgrad(dz, st.wt(L.fc_w))
-        del dzq
+        dz = eng.dgrad(_Act(dx2), st.wt(L.proj_w), act=QGELU, dact=z, q8=True)
+        _wgrad(dz.t, hn2, st.g(L.fc_w), st.g(L.fc_b))
+        dhn2 = eng.dgrad(dz, st.wt(L.fc_w)).t
         del dz
         dx1 = torch.empty_like(h)
-        # bf16 / fp32: out_proj's bias gradient = the column sums of dx1, taken by its LN backward
-        lnsum = LN_BIAS["on"] and not f8
-        dx1q = (N.layernorm_bwd_mxfp8 if f8 else N.layernorm_bwd)(
-            R, W, dhn2, _rows(W), x1, _rows(W), m2, r2, st.f32(L.ln2_w), dx1, _rows(W), dx2, _rows(W),
-            st.g(L.ln2_w), st.g(L.ln2_b), **({"dsum": st.g(L.out_b), "dsum_with_dres": True} if lnsum else {}))
-        _wgrad(dx1, o, st.g(L.out_w), None if lnsum else st.g(L.out_b))
-        do = dg(dx1, st.wt(L.out_w), dyq=dx1q) if f8 else _dgrad(dx1, st.wt(L.out_w))
-        dqkv = torch.empty_like(qkv)
-        delta = torch.empty(P, heads, T, device=h.device)
-        dqkvq = None
-        if f8:
-            dqkvq = N.attn_bwd_mxfp8(P, T, heads, qkv, None, 1.0 / math.sqrt(W // heads), o, do, lse,
-                                     delta, dqkv)
-        else:
-            N.attn_bwd(P, T, heads, qkv, 3 * W, 0, W, 2 * W, None, 1.0 / math.sqrt(W // heads), o, W,
-                       do, W, lse, delta, dqkv, 3 * W)
-        _wgrad(dqkv, hn, st.g(L.in_w), st.g(L.in_b))
-        dhn = dg(dqkv, st.wt(L.in_w), dyq=dqkvq) if f8 else _dgrad(dqkv, st.wt(L.in_w))
+        # out_proj's output gradient is dx1 = LN gradient + dx2, so its bias gradient is the column
+        # sums of dx1 INCLUDING the residual gradient: said with dsum_with_dres
+        g1, gb = eng.ln_bwd(dhn2, x1, m2, r2, st.f32(L.ln2_w), dx1, dx2, st.g(L.ln2_w), st.g(L.ln2_b),
+                            st.g(L.out_b), dsum_with_dres=True)
+        _wgrad(dx1, o, st.g(L.out_w), gb)
+        do = eng.dgrad(g1, st.wt(L.out_w)).t
+        del g1
+        dqkv = eng.attn_bwd(P, T, heads, qkv, None, o, do, lse)
+        _wgrad(dqkv.t, hn, st.g(L.in_w), st.g(L.in_b))
+        dhn = eng.dgrad(dqkv, st.wt(L.in_w)).t
         dh = torch.empty_like(h)
         N.layernorm_bwd(R, W, dhn, _rows(W), h, _rows(W), m1, r1, st.f32(L.ln1_w), dh, _rows(W),
                         dx1, _rows(W), st.g(L.ln1_w), st.g(L.ln1_b))
         st.grad_ready(L.span)
-        _fp8_bwd_done(f8)
+        eng.bwd_done()
         return dh, None, None, None, None, None, None, None
 
 
