@@ -602,6 +602,85 @@ mmseq_status mmseq_order_score(int B, int N, int H, int K, const float* doc, con
                                mmseq_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Ancestral samples from the pointer decoder: S orders per story drawn step by step from the
+ * distributions mmseq_order_score scores. Sample s of story b is a beam slot that never branches
+ * (the setup, the step and the kernels of mmseq_beam_search; W = nb = S, every step entered with
+ * score 0, so the step's row is r[j] = -logp_t[j]); at step t = 0 .. N-2 its pick is
+ *   h      = lowbias32(lowbias32((uint32_t)e ^ k0) + ((uint32_t)(e >> 32) ^ k1)), (k0, k1) the
+ *            key of (seed, stream_id) as in mmseq_mlm_mask, at the 64-bit element
+ *            e = (story0 + b) * 2^32 + (sample0 + s) * (N - 1) + t
+ *   u      = (h >> 8) * 2^-24                                   in [0, 1)
+ *   total  = sum over the unpointed j, ascending, of expf(-r[j])          (fp32)
+ *   pick   = the first unpointed j, ascending, whose running fp32 sum of expf(-r[j]) exceeds
+ *            u * total; the last unpointed j when none does
+ * and nll[b][s] += r[pick] in step order; the last position takes the one step left. N = 1 gives
+ * the order [0] and nll 0. A sample is a pure function of (weights, inputs, seed, stream_id,
+ * story0 + b, sample0 + s, t): a call for S samples from sample0 = 0 and calls for parts of them
+ * with their sample0 (or parts of the stories with their story0) draw the same picks; their nll
+ * agree to fp32 GEMM rounding where the row counts of the dense parts differ.
+ *   doc .. b_t   as mmseq_beam_search
+ *   orders       [B][S][N] int64, nll [B][S] f32                                   outputs
+ *   u            [B][S][N-1] f32 or NULL: the uniforms drawn
+ *   step_nlp     [B][S][N-1][N] f32 or NULL: the rows sampled from, +INFINITY where pointed
+ * Supported: N, H, B as mmseq_order_score with K = S (else MMSEQ_EUNSUPPORTED, nothing launched);
+ * story0, sample0 >= 0, story0 + B < 2^31, (sample0 + S) * 16 < 2^31, no null buffer (u and
+ * step_nlp excepted), workspace of mmseq_order_sample_workspace(B, N, H, S) bytes (0 for an
+ * unsupported shape), 16-byte aligned, contents irrelevant on entry; else MMSEQ_EINVAL. Nothing
+ * is written outside the outputs and the workspace; two calls on the same inputs give
+ * bit-identical outputs; no atomics. Stream ordering as for mmseq_beam_search.
+ * ------------------------------------------------------------------------------------------ */
+int64_t mmseq_order_sample_workspace(int B, int N, int H, int S);
+mmseq_status mmseq_order_sample(int B, int N, int H, int S, const float* doc, const float* okey,
+                                const float* hist, const float* h0, const float* c0,
+                                const float* w_ih, const float* b_ih, const float* w_hh,
+                                const float* b_hh, const float* w_q, const float* b_q,
+                                const float* w_pw, const float* w_t, const float* b_t,
+                                uint64_t seed, uint32_t stream_id, int story0, int sample0,
+                                int64_t* orders, float* nll, float* u, float* step_nlp,
+                                void* workspace, int64_t workspace_bytes, mmseq_stream stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Posterior over K candidate orders per story (csrc/posterior.hip): from their pointer NLLs to
+ * marginals, the heaviest candidate and the minimum-risk candidates under the per-story metrics
+ * of evaluate.cal_result. One workgroup per story; every sum is taken in f64 in ascending
+ * candidate order and rounded once to f32; no atomics, bit-identical between calls.
+ *   orders  int64; candidate k of story b starts at orders + b * story_stride + k * N
+ *           (story_stride = 0: one list [K][N] for all stories; K * N: [B][K][N])
+ *   nll     [B][K] f32
+ *   valid   a candidate is valid iff its nll is finite and its N entries are a permutation of
+ *           0 .. N-1 (checked before any entry is used as an index); the others weigh 0: +inf
+ *           scores, the n-best list's padding rows (order -1, score +inf), samples that failed
+ *   mode 0  w_k = exp(m - nll_k), m the smallest valid nll (weights proportional to exp(-nll))
+ *   mode 1  w_k = 1 (a list of samples: uniform; a repeated order counts as often as it occurs)
+ *   Z = sum w_k, p_k = w_k / Z over the valid candidates
+ * Outputs per story (f32 unless stated):
+ *   logz               log Z - m (mode 0: logsumexp(-nll), the log of the mass the list covers);
+ *                      log(valid count) (mode 1)
+ *   position [N][N]    position[t][s] = sum of p_k over the candidates with step s at position t
+ *   before   [N][N]    before[a][c]   = sum of p_k over those where a precedes c; diagonal 0
+ *   entropy            -sum p_k log p_k, nats
+ *   map_index int32, map_prob      the heaviest candidate (the smallest nll; the first valid one
+ *                      in mode 1), ties (-0.0 and +0.0 tie) to the lowest index, and its p
+ *   mbr_acc_index, mbr_tau_index int32, exp_acc, exp_tau     the valid candidates with the largest
+ *                      gain_acc(o) = (sum_t position[t][o_t]) / N                  t ascending
+ *                      gain_tau(o) = (sum_{i<j} before[o_i][o_j] - before[o_j][o_i]) / C(N, 2)
+ *                                    (i, j) lexicographic; 1 for N = 1
+ *                      computed in f64 from the f32-rounded matrices in the order stated, ties to
+ *                      the lowest index, and those gains: the expectations under p of
+ *                      cal_result's per-story accuracy and Kendall's tau of o
+ * A story without a valid candidate gets logz = -INFINITY, zero matrices, indices -1 and 0 in the
+ * other outputs. Nothing is written outside the outputs' declared extents.
+ * Supported: B >= 0, 1 <= N <= 16, K >= 1, else MMSEQ_EUNSUPPORTED with nothing launched; a mode
+ * other than 0 / 1, a null buffer or a story_stride that is neither 0 nor >= K * N MMSEQ_EINVAL.
+ * ------------------------------------------------------------------------------------------ */
+mmseq_status mmseq_order_posterior(int B, int N, int K, int mode, const int64_t* orders,
+                                   int64_t story_stride, const float* nll, float* logz,
+                                   float* position, float* before, float* entropy,
+                                   int32_t* map_index, float* map_prob, int32_t* mbr_acc_index,
+                                   int32_t* mbr_tau_index, float* exp_acc, float* exp_tau,
+                                   mmseq_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * MX-fp8 forward GEMMs (BASELINE config 5 "fp8 MFMA"; v_mfma_scale_f32_16x16x128_f8f6f4).
  *  Format: OCP e4m3 elements, one E8M0 scale (2^(s-127)) per 32 consecutive K-elements of a row
  *  (OCP MX: s = floor(log2 amax) - 8 + 127, elements = x / 2^(s-127) clamped to +-448, RNE).

@@ -160,6 +160,12 @@ _SIGS = {
     "mmseq_order_score_workspace": (ctypes.c_int64, [ctypes.c_int] * 4),
     "mmseq_order_score": (ctypes.c_int, [ctypes.c_int] * 4 + [_vp] * 15 + [_c_i64] +
                           [_vp] * 3 + [_c_i64, _vp]),
+    "mmseq_order_sample_workspace": (ctypes.c_int64, [ctypes.c_int] * 4),
+    "mmseq_order_sample": (ctypes.c_int, [ctypes.c_int] * 4 + [_vp] * 14 +
+                           [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_int] +
+                           [_vp] * 5 + [_c_i64, _vp]),
+    "mmseq_order_posterior": (ctypes.c_int, [ctypes.c_int] * 4 + [_vp, _c_i64] + [_vp] * 11 +
+                              [_vp]),
     "mmseq_mxfp8_scale_bytes": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int]),
     "mmseq_quant_mxfp8": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _c_i64, ctypes.c_int,
                                          _vp, _c_i64, _vp, _vp]),
@@ -735,6 +741,72 @@ def order_score(doc, okey, hist, h0, c0, weights, orders, nll, step_nll, workspa
                                  _p(workspace), _ws_bytes(workspace), _stream())
     if st != EUNSUPPORTED:
         _check(st, "mmseq_order_score")
+    return st
+
+
+def order_sample_workspace(B, N, H, S):
+    """Bytes of workspace mmseq_order_sample needs; 0 where the shape is unsupported."""
+    return int(lib().mmseq_order_sample_workspace(B, N, H, S))
+
+
+def order_sample(doc, okey, hist, h0, c0, weights, seed, stream_id, story0, sample0, orders, nll,
+                 u, step_nlp, workspace):
+    """mmseq_order_sample: the inputs of beam_search; orders int64 [B][S][N], nll f32 [B][S], u f32
+    [B][S][N-1] or None, step_nlp f32 [B][S][N-1][N] or None; workspace of at least
+    order_sample_workspace(B, N, H, S) bytes. Returns the status for MMSEQ_EUNSUPPORTED and
+    raises on every other failure."""
+    B, N, H = doc.shape
+    if orders.dim() != 3:
+        raise ValueError("order_sample: orders must be int64 [B][S][N]")
+    S = int(orders.shape[1])
+    extra = [(orders, torch.int64, (B, S, N)), (nll, torch.float32, (B, S))]
+    if u is not None:
+        extra.append((u, torch.float32, (B, S, N - 1)))
+    if step_nlp is not None:
+        extra.append((step_nlp, torch.float32, (B, S, N - 1, N)))
+    ptrs = _beam_inputs("order_sample", doc, okey, hist, h0, c0, weights, extra)
+    st = lib().mmseq_order_sample(B, N, H, S, *ptrs, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                  int(stream_id) & 0xFFFFFFFF, int(story0), int(sample0),
+                                  _p(orders), _p(nll), _p(u), _p(step_nlp), _p(workspace),
+                                  _ws_bytes(workspace), _stream())
+    if st != EUNSUPPORTED:
+        _check(st, "mmseq_order_sample")
+    return st
+
+
+POSTERIOR_MODES = {"weights": 0, "uniform": 1}
+# name -> (dtype, trailing shape in units of N) of mmseq_order_posterior's outputs, in ABI order
+POSTERIOR_OUTPUTS = (("logz", torch.float32, 0), ("position", torch.float32, 2),
+                     ("before", torch.float32, 2), ("entropy", torch.float32, 0),
+                     ("map_index", torch.int32, 0), ("map_prob", torch.float32, 0),
+                     ("mbr_acc_index", torch.int32, 0), ("mbr_tau_index", torch.int32, 0),
+                     ("exp_acc", torch.float32, 0), ("exp_tau", torch.float32, 0))
+
+
+def order_posterior(orders, nll, mode, out):
+    """mmseq_order_posterior: orders int64 [K][N] or [B][K][N], nll f32 [B][K], mode 0 / 1, out:
+    dict name -> contiguous device tensor for every entry of POSTERIOR_OUTPUTS ([B], or [B][N][N]
+    for the two matrices). Returns the status for MMSEQ_EUNSUPPORTED and raises on every other
+    failure."""
+    if nll.dim() != 2 or orders.dim() not in (2, 3):
+        raise ValueError("order_posterior: nll must be [B][K], orders [K][N] or [B][K][N]")
+    B, K = nll.shape
+    N = int(orders.shape[-1])
+    oshape = (K, N) if orders.dim() == 2 else (B, K, N)
+    checks = [(orders, torch.int64, oshape), (nll, torch.float32, (B, K))]
+    for name, dtype, nn in POSTERIOR_OUTPUTS:
+        checks.append((out[name], dtype, (B,) + (N,) * nn))
+    _dev(*(t for t, _, _ in checks))
+    for t, dtype, shp in checks:
+        if t.dtype != dtype or tuple(t.shape) != shp or not t.is_contiguous():
+            raise ValueError(f"order_posterior: contiguous {dtype} {shp} expected, got "
+                             f"{tuple(t.shape)} {t.dtype}")
+    st = lib().mmseq_order_posterior(B, N, K, int(mode), _p(orders),
+                                     0 if orders.dim() == 2 else K * N, _p(nll),
+                                     *(_p(out[name]) for name, _, _ in POSTERIOR_OUTPUTS),
+                                     _stream())
+    if st != EUNSUPPORTED:
+        _check(st, "mmseq_order_posterior")
     return st
 
 

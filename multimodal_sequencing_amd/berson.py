@@ -477,16 +477,31 @@ def berson_pointer_network_batch(args, model, tokenizer, inputs, decode="beam"):
     """Ordering indices for the B >= 1 stories of `inputs` (same keys as berson_pointer_network)
     -> list of B lists. decode="beam": the device-resident beam search. decode="exact": the
     arg-min over all N! orders (exact_order_batch, N <= 7); `model.last_beam_scores` then holds
-    the exact optimum's scores."""
-    if decode not in ("beam", "exact"):
-        raise ValueError(f"decode must be 'beam' or 'exact', got {decode!r}")
+    the exact optimum's scores. decode="mbr_acc" / "mbr_tau": the order with the largest expected
+    positional accuracy / Kendall's tau under the decoder's own distribution
+    (order_posterior_batch: all N! orders for N <= 7, above that args.mbr_samples (256) ancestral
+    samples with seed args.mbr_seed (0)); `model.last_beam_scores` then holds the chosen orders'
+    pointer NLLs. berson_evaluate takes any of them as its `pointer_network_batch`, e.g.
+    functools.partial(berson_pointer_network_batch, decode="mbr_tau")."""
+    if decode not in ("beam", "exact", "mbr_acc", "mbr_tau"):
+        raise ValueError("decode must be 'beam', 'exact', 'mbr_acc' or 'mbr_tau', "
+                         f"got {decode!r}")
     berson = _batch_inputs(model, inputs)
     if decode == "beam":
         return beam_search_pointer_batch(args, model, **berson)
     with torch.no_grad():
         enc = model.encode(**berson)
-        order, model.last_beam_scores, _ = exact_order_batch(args, model, enc)
-    return order.tolist()
+        if decode == "exact":
+            order, model.last_beam_scores, _ = exact_order_batch(args, model, enc)
+            return order.tolist()
+        N = enc[0].shape[1]
+        post = order_posterior_batch(args, model, enc,
+                                     source="exact" if N <= EXACT_MAX_N else "sample",
+                                     samples=int(getattr(args, "mbr_samples", 256)),
+                                     seed=int(getattr(args, "mbr_seed", 0)))
+        idx = post[decode + "_index"].to(torch.int64).clamp_(min=0)
+        model.last_beam_scores = post["nll"].gather(1, idx[:, None])[:, 0]
+    return post[decode + "_order"].tolist()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -702,3 +717,150 @@ def beam_nbest_batch(args, model, enc):
                                          [model.store.f32(n) for n in _BEAM_WEIGHTS], W, orders,
                                          scores, count, ws), "mmseq_beam_search_nbest")
     return orders, scores, count
+
+
+# ------------------------------------------------------------------------------------------------
+# Posterior over orders, sampling and minimum-risk decode.
+def _gather_orders(orders, index):
+    """orders [K][N] or [B][K][N], index int32 [B] (-1: none) -> int64 [B][N], -1 rows for -1."""
+    idx = index.to(torch.int64)
+    safe = idx.clamp(min=0)
+    rows = orders[safe] if orders.dim() == 2 else \
+        orders.gather(1, safe[:, None, None].expand(-1, 1, orders.shape[-1]))[:, 0]
+    return torch.where(idx[:, None] >= 0, rows, torch.full_like(rows, -1))
+
+
+@torch.no_grad()
+def order_posterior(orders, nll, mode="weights"):
+    """Scored candidate orders -> their posterior (mmseq_order_posterior). orders: int64 device
+    tensor [K][N] (one list for all stories) or [B][K][N]; nll f32 [B][K], +inf (or an order that
+    is no permutation, such as the n-best list's -1 rows) = absent. mode="weights": p_k
+    proportional to exp(-nll_k) (enumerations, n-best lists); "uniform": every valid row weighs
+    the same (samples). -> dict of device tensors: logz, entropy, map_prob, exp_acc, exp_tau f32
+    [B]; position, before f32 [B][N][N]; map_index, mbr_acc_index, mbr_tau_index int32 [B]; and
+    the orders behind the three indices, map_order, mbr_acc_order, mbr_tau_order int64 [B][N]
+    (gathered on the device; -1 where a story has no valid candidate). Nothing synchronises."""
+    if mode not in N_.POSTERIOR_MODES:
+        raise ValueError(f"mode must be 'weights' or 'uniform', got {mode!r}")
+    if not (torch.is_tensor(orders) and torch.is_tensor(nll) and orders.is_cuda and nll.is_cuda):
+        raise ValueError("order_posterior: orders and nll must be device tensors")
+    if orders.dtype != torch.int64 or nll.dtype != torch.float32 or nll.dim() != 2 or \
+            orders.dim() not in (2, 3) or orders.shape[-2] != nll.shape[1] or \
+            (orders.dim() == 3 and orders.shape[0] != nll.shape[0]):
+        raise ValueError("order_posterior: orders int64 [K][N] or [B][K][N] and nll f32 [B][K] "
+                         f"expected, got {orders.dtype} {tuple(orders.shape)} and {nll.dtype} "
+                         f"{tuple(nll.shape)}")
+    B, N = nll.shape[0], orders.shape[-1]
+    orders, nll = orders.contiguous(), nll.contiguous()
+    out = {name: torch.empty((B,) + (N,) * nn, dtype=dtype, device=nll.device)
+           for name, dtype, nn in N_.POSTERIOR_OUTPUTS}
+    N_._check_shape(N_.order_posterior(orders, nll, N_.POSTERIOR_MODES[mode], out),
+                    "mmseq_order_posterior")
+    for name in ("map", "mbr_acc", "mbr_tau"):
+        out[name + "_order"] = _gather_orders(orders, out[name + "_index"])
+    return out
+
+
+def _sample_chunk(B, N, H, S):
+    """_score_chunk for the sampler's workspace."""
+    sc = S
+    while sc > 1:
+        nbytes = N_.order_sample_workspace(B, N, H, sc)
+        if 0 < nbytes <= SCORE_WS_CAP:
+            return sc, nbytes
+        sc = (sc + 1) // 2
+    return 1, N_.order_sample_workspace(B, N, H, 1)
+
+
+@torch.no_grad()
+def sample_orders_batch(args, model, enc, samples, seed, stream_id=0, return_steps=False):
+    """`samples` ancestral samples from the pointer decoder for every story of an encode() tuple
+    (mmseq_order_sample) -> (orders int64 [B][S][N], nll f32 [B][S]) on the device, with
+    return_steps=True also (u f32 [B][S][N-1], step_nlp f32 [B][S][N-1][N]): the uniforms drawn
+    and the rows of -log p sampled from (+inf where pointed). Sample s of story b depends on
+    (seed, stream_id, b, s) only: the first S' of S samples are the samples of a call for S'.
+    S is split like score_orders_batch's K to keep the workspace within SCORE_WS_CAP. An
+    unsupported shape (N > 16) raises _native.Unsupported: there is no host sampler."""
+    (sent, _p, dec_init, okeys, _cls, cls_mat, _cs, cs_mat, _h1, _h2) = enc
+    B, N, H = sent.shape
+    S = int(samples)
+    if S < 1:
+        raise ValueError(f"samples must be >= 1, got {samples}")
+    dev = sent.device
+    sc, nbytes = _sample_chunk(B, N, H, S)
+    if nbytes == 0:
+        raise N_.Unsupported(f"sample_orders_batch: B={B} N={N} H={H} S={S} is outside "
+                             "mmseq_order_sample's limits")
+    orders = torch.empty(B, S, N, dtype=torch.int64, device=dev)
+    nll = torch.empty(B, S, dtype=torch.float32, device=dev)
+    u = steps = None
+    if return_steps:
+        u = torch.empty(B, S, max(N - 1, 0), dtype=torch.float32, device=dev)
+        steps = torch.empty(B, S, max(N - 1, 0), N, dtype=torch.float32, device=dev)
+    hist = torch.cat([cls_mat, torch.softmax(cs_mat, -1)], -1).contiguous()
+    ins = (sent.contiguous(), okeys.contiguous(), hist, dec_init[0][0].contiguous(),
+           dec_init[1][0].contiguous(), [model.store.f32(n) for n in _BEAM_WEIGHTS])
+    cache = model.__dict__.setdefault("_score_ws", {})
+    for s0 in range(0, S, sc):
+        s = min(sc, S - s0)
+        nb = nbytes if s == sc else N_.order_sample_workspace(B, N, H, s)
+        ws = cache.get((B, N, H, s))  # the scorer's layout: one cache serves both
+        if ws is None or ws.numel() * 4 < nb:
+            ws = cache[(B, N, H, s)] = torch.empty(nb // 4, dtype=torch.float32, device=dev)
+        whole = s == S
+        o_c = orders if whole else torch.empty(B, s, N, dtype=torch.int64, device=dev)
+        n_c = nll if whole else torch.empty(B, s, dtype=torch.float32, device=dev)
+        u_c = st_c = None
+        if return_steps:
+            u_c = u if whole else torch.empty(B, s, N - 1, dtype=torch.float32, device=dev)
+            st_c = steps if whole else torch.empty(B, s, N - 1, N, dtype=torch.float32, device=dev)
+        N_._check_shape(N_.order_sample(*ins, seed, stream_id, 0, s0, o_c, n_c, u_c, st_c, ws),
+                        "mmseq_order_sample")
+        if not whole:
+            orders[:, s0:s0 + s] = o_c
+            nll[:, s0:s0 + s] = n_c
+            if return_steps:
+                u[:, s0:s0 + s] = u_c
+                steps[:, s0:s0 + s] = st_c
+    return (orders, nll, u, steps) if return_steps else (orders, nll)
+
+
+@torch.no_grad()
+def order_posterior_batch(args, model, enc, source="exact", samples=256, seed=0):
+    """The posterior over orders of every story of an encode() tuple -> order_posterior's dict
+    plus "orders" and "nll", the candidates it was taken over.
+    source="exact":  all N! orders (itertools.permutations order) through score_orders_batch;
+                     logz is 0 up to rounding. N <= 7; ValueError above.
+    source="nbest":  the beam's finished hypotheses (beam_nbest_batch); logz <= 0 is the log of
+                     the mass the list covers, and the marginals are those of the list alone.
+    source="sample": `samples` ancestral samples (sample_orders_batch, seed), weighted uniformly:
+                     the unbiased estimate for N > 7, where the n-best list is a biased sample."""
+    import itertools
+    B, N, _H = enc[0].shape
+    if source == "exact":
+        if N > EXACT_MAX_N:
+            raise ValueError(f"order_posterior_batch enumerates N! orders: N = {N} exceeds "
+                             f"{EXACT_MAX_N}")
+        orders = torch.tensor(list(itertools.permutations(range(N))), dtype=torch.int64,
+                              device=enc[0].device)
+        nll = score_orders_batch(args, model, enc, orders)
+        mode = "weights"
+    elif source == "nbest":
+        orders, nll, _count = beam_nbest_batch(args, model, enc)
+        mode = "weights"
+    elif source == "sample":
+        orders, nll = sample_orders_batch(args, model, enc, samples, seed)
+        mode = "uniform"
+    else:
+        raise ValueError(f"source must be 'exact', 'nbest' or 'sample', got {source!r}")
+    post = order_posterior(orders, nll, mode)
+    post["orders"], post["nll"] = orders, nll
+    return post
+
+
+def berson_order_posterior(args, model, tokenizer, inputs, source="exact", samples=256, seed=0):
+    """The posterior over orders for the B >= 1 stories of `inputs` (same keys as
+    berson_pointer_network_batch): one encode, then order_posterior_batch."""
+    with torch.no_grad():
+        enc = model.encode(**_batch_inputs(model, inputs))
+        return order_posterior_batch(args, model, enc, source, samples, seed)

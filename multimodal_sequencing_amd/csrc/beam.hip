@@ -19,6 +19,8 @@
 // mmseq_beam_search_nbest reports every finished hypothesis of the last selection, and
 // mmseq_order_score runs K candidate orders per story as slots that never branch (W = nb = K,
 // every slot entered with score 0) and, instead of selecting, adds each slot's own pick to its nll.
+// mmseq_order_sample runs S such slots per story whose pick at every step is DRAWN from the step's
+// distribution (ancestral sampling) with the counter hash of mmseq_mlm_mask.
 #include "common.h"
 
 namespace {
@@ -348,6 +350,80 @@ __global__ __launch_bounds__(256) void order_pick_kernel(int64_t R, int N, int t
   if (step_nll) step_nll[slot * (N - 1) + t] = v;
 }
 
+// mmseq_order_sample, one workgroup per slot (story b, sample s): (h, c) <- (h0, c0), nll <- 0 and
+// the score every step is entered with <- 0. N == 1: the order is [0].
+__global__ __launch_bounds__(256) void sample_init_kernel(int N, int H, int S,
+                                                          const float* __restrict__ h0,
+                                                          const float* __restrict__ c0,
+                                                          float* __restrict__ h, float* __restrict__ c,
+                                                          float* __restrict__ zero,
+                                                          int64_t* __restrict__ orders,
+                                                          float* __restrict__ nll) {
+  const int64_t slot = blockIdx.x;
+  const int b = (int)(slot / S);
+  if (threadIdx.x == 0) {
+    nll[slot] = 0.f;
+    if (N == 1) orders[slot] = 0;
+  }
+  if (N == 1) return;
+  if (threadIdx.x == 0) zero[slot] = 0.f;
+  for (int u = threadIdx.x; u < H; u += 256) {
+    h[slot * H + u] = h0[(int64_t)b * H + u];
+    c[slot * H + u] = c0[(int64_t)b * H + u];
+  }
+}
+
+// One thread per slot after beam_score_kernel of step t (entered with score 0, so s = -logp): the
+// slot's t-th pick by inversion of the step's distribution. u = (h >> 8) 2^-24 from the counter
+// hash of mmseq_mlm_mask (two lowbias32 rounds) at element (story0 + b) 2^32 + (sample0 + s)(N-1)
+// + t; j ascends over the unpointed steps with a running f32 sum of exp(-s_j) and the first j whose
+// sum exceeds u * total is taken (total: the same sum to the end), else the last unpointed one.
+__global__ __launch_bounds__(256) void sample_pick_kernel(int64_t R, int N, int S, int t,
+                                                          uint32_t k0, uint32_t k1, uint32_t story0,
+                                                          uint32_t sample0,
+                                                          const float* __restrict__ s,
+                                                          int* __restrict__ seq,
+                                                          int64_t* __restrict__ orders,
+                                                          float* __restrict__ nll,
+                                                          float* __restrict__ u_out,
+                                                          float* __restrict__ step_nlp) {
+  const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (slot >= R) return;
+  const uint32_t b = (uint32_t)(slot / S), smp = (uint32_t)(slot % S);
+  const uint32_t lo = (sample0 + smp) * (uint32_t)(N - 1) + (uint32_t)t, hi = story0 + b;
+  const uint32_t h = drop_mix(drop_mix(lo ^ k0) + (hi ^ k1));
+  const float u = (float)(h >> 8) * 0x1p-24f;
+  unsigned pointed = 0;
+  for (int p = 0; p < t; ++p) pointed |= 1u << seq[slot * BEAM_MAXN + p];
+  const float* row = s + slot * N;
+  float total = 0.f;
+  for (int j = 0; j < N; ++j)
+    if (!((pointed >> j) & 1u)) total += expf(-row[j]);
+  const float thr = u * total;
+  float run = 0.f;
+  int pick = -1, last = 0;
+  for (int j = 0; j < N; ++j) {
+    if ((pointed >> j) & 1u) continue;
+    run += expf(-row[j]);
+    last = j;
+    if (pick < 0 && run > thr) pick = j;
+  }
+  if (pick < 0) pick = last;
+  seq[slot * BEAM_MAXN + t] = pick;
+  nll[slot] += row[pick];
+  orders[slot * N + t] = pick;
+  if (t == N - 2) {  // the last position is the one step left
+    const unsigned have = pointed | (1u << pick);
+    int miss = 0;
+    while ((have >> miss) & 1u) ++miss;
+    orders[slot * N + N - 1] = miss;
+  }
+  if (u_out) u_out[slot * (N - 1) + t] = u;
+  if (step_nlp)
+    for (int j = 0; j < N; ++j)
+      step_nlp[(slot * (N - 1) + t) * N + j] = ((pointed >> j) & 1u) ? INFINITY : row[j];
+}
+
 inline bool beam_supported(int B, int N, int H, int W) {
   return B >= 0 && N >= 1 && N <= BEAM_MAXN && W >= 1 && W <= BEAM_MAXW && H >= 1 &&
          (int64_t)B * BEAM_MAXW * BEAM_MAXN * 4 < INT32_MAX / 2 && (int64_t)H * 4 * 4 < INT32_MAX / 2;
@@ -538,6 +614,65 @@ extern "C" mmseq_status mmseq_order_score(int B, int N, int H, int K, const floa
     hipLaunchKernelGGL(order_pick_kernel, dim3((R + 255) / 256), dim3(256), 0, st, (int64_t)R, N, t,
                        ws + L.s, seq, bad, nll, step_nll);
     if ((e = mmseq_check_launch("order_pick")) != MMSEQ_OK) return e;
+  }
+  return MMSEQ_OK;
+}
+
+extern "C" int64_t mmseq_order_sample_workspace(int B, int N, int H, int S) {
+  if (!score_supported(B, N, H, S)) return 0;
+  return score_layout(B, N, H, S).total * 4;
+}
+
+extern "C" mmseq_status mmseq_order_sample(int B, int N, int H, int S, const float* doc,
+                                           const float* okey, const float* hist, const float* h0,
+                                           const float* c0, const float* w_ih, const float* b_ih,
+                                           const float* w_hh, const float* b_hh, const float* w_q,
+                                           const float* b_q, const float* w_pw, const float* w_t,
+                                           const float* b_t, uint64_t seed, uint32_t stream_id,
+                                           int story0, int sample0, int64_t* orders, float* nll,
+                                           float* u, float* step_nlp, void* workspace,
+                                           int64_t workspace_bytes, mmseq_stream stream) {
+  if (!score_supported(B, N, H, S))
+    return mmseq_set_error(MMSEQ_EUNSUPPORTED,
+                           "order_sample: B=%d N=%d H=%d S=%d outside 1 <= N <= %d, 1 <= S, "
+                           "B*S*4H < 2^31 (or B / H too large for 32-bit row counts)",
+                           B, N, H, S, BEAM_MAXN);
+  MMSEQ_REQUIRE(doc && okey && hist && h0 && c0 && w_ih && b_ih && w_hh && b_hh && w_q && b_q &&
+                    w_pw && w_t && b_t && orders && nll,
+                "order_sample: null buffer");
+  MMSEQ_REQUIRE(story0 >= 0 && sample0 >= 0 && (int64_t)story0 + B < INT32_MAX &&
+                    ((int64_t)sample0 + S) * BEAM_MAXN < INT32_MAX,
+                "order_sample: story0 %d / sample0 %d negative or beyond the 32-bit counter words",
+                story0, sample0);
+  const ScoreWs L = score_layout(B, N, H, S);  // the scorer's layout; its `bad` row is not used
+  MMSEQ_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= L.total * 4,
+                "order_sample: workspace must be 16-byte aligned and hold %lld bytes (got %lld)",
+                (long long)(L.total * 4), (long long)workspace_bytes);
+  if (B == 0) return MMSEQ_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  float* ws = reinterpret_cast<float*>(workspace);
+  const int R = B * S;
+  int* seq = reinterpret_cast<int*>(ws + L.seq);
+  hipLaunchKernelGGL(sample_init_kernel, dim3(R), dim3(256), 0, st, N, H, S, h0, c0, ws + L.h,
+                     ws + L.c, ws + L.zero, orders, nll);
+  mmseq_status e = mmseq_check_launch("sample_init");
+  if (e != MMSEQ_OK || N == 1) return e;
+  const mmseq_dropout key = {0.5f, stream_id, seed};  // the dropout key schedule; p is not used
+  const Drop d = make_drop(&key);
+  const BeamWeights wt{w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t};
+  const int64_t pstride = up4((int64_t)B * N * N * H);
+  if ((e = beam_story_setup(B, N, H, doc, hist, wt, ws + L.gx, ws + L.proj, pstride, stream)) !=
+      MMSEQ_OK)
+    return e;
+  for (int t = 0; t < N - 1; ++t) {  // every slot is live (nb = S) and enters with score 0
+    if ((e = beam_step(B, N, H, S, t, S, wt, okey, ws + L.gx, ws + L.proj, pstride, seq,
+                       ws + L.zero, ws + L.h, ws + L.c, ws + L.gh, ws + L.q, ws + L.s, stream)) !=
+        MMSEQ_OK)
+      return e;
+    hipLaunchKernelGGL(sample_pick_kernel, dim3((R + 255) / 256), dim3(256), 0, st, (int64_t)R, N, S,
+                       t, d.k0, d.k1, (uint32_t)story0, (uint32_t)sample0, ws + L.s, seq, orders,
+                       nll, u, step_nlp);
+    if ((e = mmseq_check_launch("sample_pick")) != MMSEQ_OK) return e;
   }
   return MMSEQ_OK;
 }
