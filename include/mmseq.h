@@ -640,6 +640,52 @@ mmseq_status mmseq_order_sample(int B, int N, int H, int S, const float* doc, co
                                 void* workspace, int64_t workspace_bytes, mmseq_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The pointer NLL of ALL N! orders of every story from the prefix tree (csrc/beam.hip, planner in
+ * csrc/order_tree_plan.h): orders that share a prefix share its LSTM / pointer steps, so every
+ * prefix of every story is stepped exactly once, sum_{t=0..N-2} N!/(N-t)! node-steps per story
+ * (N = 9: 260 650) instead of the N! (N-1) (2 903 040) of mmseq_order_score over the same list.
+ * The step is mmseq_beam_search's (the same setup and kernels); a child enters with its parent's
+ * s entry (score - logp) of its pick, so
+ *   nll[b][k] = the running fp32 sum, in step order, of -logp_t[o_t], t = 0 .. N-2, o the k-th
+ *               permutation of 0 .. N-1 in lexicographic order (itertools.permutations(range(N))),
+ * as mmseq_order_score defines it; the two agree to fp32 GEMM rounding (the dense parts run at
+ * other row counts), not bit for bit. Only N - 1 steps run, the last position is implied; N = 1
+ * gives nll 0 with nothing launched but the write, N = 2 is a single step.
+ * Indexing: a node of level t (t picks made) with index i has the children i (N-t) + r, r counting
+ * the still-unpointed steps in ascending order; a node of level N-1 is its order's rank k.
+ *   doc .. b_t   as mmseq_beam_search
+ *   rows         the caller's cap on the slot rows (over all B stories) one chunk of one level may
+ *                hold, >= B * N. Level t owns one state buffer of min(N!/(N-t)!, rows / B) nodes
+ *                per story; the tree is walked in chunks (the same node range of every story),
+ *                each stepped and then descended below before the next is taken, so any `rows` in
+ *                range gives the same set of node-steps. rows beyond (2^31 - 2) / max(4H, 16)
+ *                counts as that (the dense parts count elements in 32 bits).
+ *   nll          [B][N!] f32                                                          output
+ *   orders       [N!][N] int64 or NULL: the same table unranked on the device, one list for all
+ *                stories (the story_stride = 0 list of mmseq_order_posterior / mmseq_order_score)
+ *   workspace    mmseq_order_tree_workspace(B, N, H, rows) bytes, a function of these four alone
+ *                (0 for an unsupported shape or rows < B * N), 16-byte aligned, contents irrelevant
+ *                on entry: every element that is read was written by this call first, NaN in it
+ *                reaches no output. Nothing is written outside nll, orders and the workspace.
+ * The schedule follows from (B, N, rows) on the host: the whole call is enqueued on `stream` with
+ * no host synchronisation and no copy to the host; no atomics; two calls on the same inputs (and
+ * the same rows) give bit-identical outputs. Calls with different `rows` agree to fp32 GEMM
+ * rounding.
+ * Supported: 1 <= N <= 9, B * N! < 2^31, B * N * 4H < 2^31, B and H within mmseq_beam_search's
+ * limits; anything else returns MMSEQ_EUNSUPPORTED before anything is launched. A null buffer
+ * (orders excepted), rows < B * N, or a short / unaligned workspace MMSEQ_EINVAL, likewise with
+ * nothing launched. Stream ordering as for mmseq_beam_search.
+ * ------------------------------------------------------------------------------------------ */
+int64_t mmseq_order_tree_workspace(int B, int N, int H, int64_t rows);
+mmseq_status mmseq_order_tree(int B, int N, int H, const float* doc, const float* okey,
+                              const float* hist, const float* h0, const float* c0,
+                              const float* w_ih, const float* b_ih, const float* w_hh,
+                              const float* b_hh, const float* w_q, const float* b_q,
+                              const float* w_pw, const float* w_t, const float* b_t, int64_t rows,
+                              float* nll, int64_t* orders, void* workspace,
+                              int64_t workspace_bytes, mmseq_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Posterior over K candidate orders per story (csrc/posterior.hip): from their pointer NLLs to
  * marginals, the heaviest candidate and the minimum-risk candidates under the per-story metrics
  * of evaluate.cal_result. One workgroup per story; every sum is taken in f64 in ascending

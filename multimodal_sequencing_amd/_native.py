@@ -5,6 +5,7 @@ error, the call raises. Every wrapper takes torch tensors that already live on t
 device and launches on torch's current stream.
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -166,6 +167,9 @@ _SIGS = {
                            [_vp] * 5 + [_c_i64, _vp]),
     "mmseq_order_posterior": (ctypes.c_int, [ctypes.c_int] * 4 + [_vp, _c_i64] + [_vp] * 11 +
                               [_vp]),
+    "mmseq_order_tree_workspace": (ctypes.c_int64, [ctypes.c_int] * 3 + [_c_i64]),
+    "mmseq_order_tree": (ctypes.c_int, [ctypes.c_int] * 3 + [_vp] * 14 + [_c_i64] + [_vp] * 3 +
+                         [_c_i64, _vp]),
     "mmseq_mxfp8_scale_bytes": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int]),
     "mmseq_quant_mxfp8": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _c_i64, ctypes.c_int,
                                          _vp, _c_i64, _vp, _vp]),
@@ -771,6 +775,31 @@ def order_sample(doc, okey, hist, h0, c0, weights, seed, stream_id, story0, samp
                                   _ws_bytes(workspace), _stream())
     if st != EUNSUPPORTED:
         _check(st, "mmseq_order_sample")
+    return st
+
+
+def order_tree_workspace(B, N, H, rows):
+    """Bytes of workspace mmseq_order_tree needs at a chunk cap of `rows` slot rows; 0 where the
+    shape is unsupported or rows < B * N."""
+    return int(lib().mmseq_order_tree_workspace(B, N, H, int(rows)))
+
+
+def order_tree(doc, okey, hist, h0, c0, weights, rows, nll, orders, workspace):
+    """mmseq_order_tree: the inputs of beam_search; rows >= B * N, the cap on the slot rows of one
+    chunk; nll f32 [B][N!]; orders int64 [N!][N] or None; workspace of at least
+    order_tree_workspace(B, N, H, rows) bytes. Returns the status for MMSEQ_EUNSUPPORTED and
+    raises on every other failure."""
+    B, N, H = doc.shape
+    K = math.factorial(N)
+    extra = [(nll, torch.float32, (B, K))]
+    if orders is not None:
+        extra.append((orders, torch.int64, (K, N)))
+    ptrs = _beam_inputs("order_tree", doc, okey, hist, h0, c0, weights, extra)
+    st = lib().mmseq_order_tree(B, N, H, *ptrs, int(rows), _p(nll),
+                                _p(orders) if orders is not None else None, _p(workspace),
+                                _ws_bytes(workspace), _stream())
+    if st != EUNSUPPORTED:
+        _check(st, "mmseq_order_tree")
     return st
 
 

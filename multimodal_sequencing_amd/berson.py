@@ -473,7 +473,7 @@ def _batch_inputs(model, inputs):
     return berson
 
 
-def berson_pointer_network_batch(args, model, tokenizer, inputs, decode="beam"):
+def berson_pointer_network_batch(args, model, tokenizer, inputs, decode="beam", enumeration=None):
     """Ordering indices for the B >= 1 stories of `inputs` (same keys as berson_pointer_network)
     -> list of B lists. decode="beam": the device-resident beam search. decode="exact": the
     arg-min over all N! orders (exact_order_batch, N <= 7); `model.last_beam_scores` then holds
@@ -482,21 +482,34 @@ def berson_pointer_network_batch(args, model, tokenizer, inputs, decode="beam"):
     (order_posterior_batch: all N! orders for N <= 7, above that args.mbr_samples (256) ancestral
     samples with seed args.mbr_seed (0)); `model.last_beam_scores` then holds the chosen orders'
     pointer NLLs. berson_evaluate takes any of them as its `pointer_network_batch`, e.g.
-    functools.partial(berson_pointer_network_batch, decode="mbr_tau")."""
+    functools.partial(berson_pointer_network_batch, decode="mbr_tau").
+    enumeration (default args.order_enumeration, else "flat") says how all N! orders are scored:
+    "flat" as above; "tree": through the prefix tree (enumerate_orders_batch), which carries
+    decode="exact" and the exact posterior of "mbr_*" up to N = TREE_MAX_N = 9; above that "exact"
+    raises and "mbr_*" samples as with "flat"."""
     if decode not in ("beam", "exact", "mbr_acc", "mbr_tau"):
         raise ValueError("decode must be 'beam', 'exact', 'mbr_acc' or 'mbr_tau', "
                          f"got {decode!r}")
+    if enumeration is None:
+        enumeration = getattr(args, "order_enumeration", "flat")
+    if enumeration not in ("flat", "tree"):
+        raise ValueError(f"enumeration must be 'flat' or 'tree', got {enumeration!r}")
+    tree = enumeration == "tree"
     berson = _batch_inputs(model, inputs)
     if decode == "beam":
         return beam_search_pointer_batch(args, model, **berson)
     with torch.no_grad():
         enc = model.encode(**berson)
         if decode == "exact":
-            order, model.last_beam_scores, _ = exact_order_batch(args, model, enc)
+            order, model.last_beam_scores, _ = exact_order_batch(
+                args, model, enc, method="tree" if tree else "flat")
             return order.tolist()
         N = enc[0].shape[1]
-        post = order_posterior_batch(args, model, enc,
-                                     source="exact" if N <= EXACT_MAX_N else "sample",
+        if tree:
+            source = "tree" if N <= TREE_MAX_N else "sample"
+        else:
+            source = "exact" if N <= EXACT_MAX_N else "sample"
+        post = order_posterior_batch(args, model, enc, source=source,
                                      samples=int(getattr(args, "mbr_samples", 256)),
                                      seed=int(getattr(args, "mbr_seed", 0)))
         idx = post[decode + "_index"].to(torch.int64).clamp_(min=0)
@@ -508,6 +521,7 @@ def berson_pointer_network_batch(args, model, tokenizer, inputs, decode="beam"):
 # Scoring candidate orders, n-best and exact decode on ONE encoder output.
 SCORE_WS_CAP = 256 << 20  # bytes of mmseq_order_score workspace per call; above it K is chunked
 EXACT_MAX_N = 7           # 7! = 5040 candidates per story
+TREE_MAX_N = 9            # 9! = 362880 leaves of the prefix tree (mmseq_order_tree)
 
 
 def check_orders(orders, B, N):
@@ -674,14 +688,75 @@ def exact_from_scores(nll):
     return idx, best, rest.min(1).values - best
 
 
+def _tree_rows(B, N, H):
+    """-> (rows, workspace bytes) for mmseq_order_tree: the chunk cap, halving from the widest
+    level's B * N! / 2 rows (unchunked) down to the minimum B * N, whose workspace fits
+    SCORE_WS_CAP (the minimum is taken whatever it needs); bytes 0 = unsupported."""
+    import math
+    low = max(B * N, 1)
+    rows = max(low, B * math.factorial(N) // 2)
+    while rows > low:
+        nbytes = N_.order_tree_workspace(B, N, H, rows)
+        if 0 < nbytes <= SCORE_WS_CAP:
+            return rows, nbytes
+        rows = max(low, (rows + 1) // 2)
+    return low, N_.order_tree_workspace(B, N, H, low)
+
+
 @torch.no_grad()
-def exact_order_batch(args, model, enc):
+def enumerate_orders_batch(args, model, enc, return_orders=False):
+    """The pointer NLL of ALL N! orders for every story of an encode() tuple through ONE
+    mmseq_order_tree: the prefix tree, every shared prefix stepped once -> nll f32 [B][N!] on the
+    device, entry k the k-th order of itertools.permutations(range(N)) (score_orders_batch's
+    result for that list, to fp32 GEMM rounding), with return_orders=True also that list, orders
+    int64 [N!][N], unranked on the device and shared by all stories. N <= TREE_MAX_N = 9;
+    ValueError above. The tree is walked in chunks of `rows` slot rows, the largest count whose
+    workspace stays within SCORE_WS_CAP; the workspace is cached on the model like the beam's.
+    A shape outside the ABI's limits raises _native.Unsupported."""
+    import math
+    (sent, _p, dec_init, okeys, _cls, cls_mat, _cs, cs_mat, _h1, _h2) = enc
+    B, N, H = sent.shape
+    if N > TREE_MAX_N:
+        raise ValueError(f"enumerate_orders_batch walks all N! orders: N = {N} exceeds "
+                         f"{TREE_MAX_N}")
+    dev = sent.device
+    rows, nbytes = _tree_rows(B, N, H)
+    if nbytes == 0:
+        raise N_.Unsupported(f"enumerate_orders_batch: B={B} N={N} H={H} is outside "
+                             "mmseq_order_tree's limits")
+    K = math.factorial(N)
+    nll = torch.empty(B, K, dtype=torch.float32, device=dev)
+    orders = torch.empty(K, N, dtype=torch.int64, device=dev) if return_orders else None
+    cache = model.__dict__.setdefault("_tree_ws", {})
+    ws = cache.get((B, N, H, rows))
+    if ws is None:
+        ws = cache[(B, N, H, rows)] = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    hist = torch.cat([cls_mat, torch.softmax(cs_mat, -1)], -1).contiguous()
+    N_._check_shape(N_.order_tree(sent.contiguous(), okeys.contiguous(), hist,
+                                  dec_init[0][0].contiguous(), dec_init[1][0].contiguous(),
+                                  [model.store.f32(n) for n in _BEAM_WEIGHTS], rows, nll, orders,
+                                  ws), "mmseq_order_tree")
+    return (nll, orders) if return_orders else nll
+
+
+@torch.no_grad()
+def exact_order_batch(args, model, enc, method="flat"):
     """The optimum over ALL N! orders (itertools.permutations order) for every story of an
-    encode() tuple, through one score_orders_batch -> (order int64 [B][N], score f32 [B], margin
-    f32 [B] = second-best minus best) on the device. Ties go to the lowest candidate index.
-    N <= 7; ValueError above."""
+    encode() tuple -> (order int64 [B][N], score f32 [B], margin f32 [B] = second-best minus
+    best) on the device. Ties go to the lowest candidate index.
+    method="flat": through one score_orders_batch; N <= 7; ValueError above.
+    method="tree": through enumerate_orders_batch (the prefix tree); N <= TREE_MAX_N = 9."""
     import itertools
+    if method not in ("flat", "tree"):
+        raise ValueError(f"method must be 'flat' or 'tree', got {method!r}")
     B, N, _H = enc[0].shape
+    if method == "tree":
+        if N > TREE_MAX_N:
+            raise ValueError(f"exact_order_batch(method='tree') enumerates N! orders: N = {N} "
+                             f"exceeds {TREE_MAX_N}")
+        nll, perms = enumerate_orders_batch(args, model, enc, return_orders=True)
+        idx, best, margin = exact_from_scores(nll)
+        return perms[idx], best, margin
     if N > EXACT_MAX_N:
         raise ValueError(f"exact_order_batch enumerates N! orders: N = {N} exceeds {EXACT_MAX_N}")
     perms = torch.tensor(list(itertools.permutations(range(N))), dtype=torch.int64,
@@ -834,7 +909,9 @@ def order_posterior_batch(args, model, enc, source="exact", samples=256, seed=0)
     source="nbest":  the beam's finished hypotheses (beam_nbest_batch); logz <= 0 is the log of
                      the mass the list covers, and the marginals are those of the list alone.
     source="sample": `samples` ancestral samples (sample_orders_batch, seed), weighted uniformly:
-                     the unbiased estimate for N > 7, where the n-best list is a biased sample."""
+                     the unbiased estimate for N > 7, where the n-best list is a biased sample.
+    source="tree":   all N! orders through the prefix tree (enumerate_orders_batch), the same
+                     list and dict as "exact". N <= TREE_MAX_N = 9; ValueError above."""
     import itertools
     B, N, _H = enc[0].shape
     if source == "exact":
@@ -845,6 +922,12 @@ def order_posterior_batch(args, model, enc, source="exact", samples=256, seed=0)
                               device=enc[0].device)
         nll = score_orders_batch(args, model, enc, orders)
         mode = "weights"
+    elif source == "tree":
+        if N > TREE_MAX_N:
+            raise ValueError(f"order_posterior_batch(source='tree') enumerates N! orders: N = {N} "
+                             f"exceeds {TREE_MAX_N}")
+        nll, orders = enumerate_orders_batch(args, model, enc, return_orders=True)
+        mode = "weights"
     elif source == "nbest":
         orders, nll, _count = beam_nbest_batch(args, model, enc)
         mode = "weights"
@@ -852,7 +935,7 @@ def order_posterior_batch(args, model, enc, source="exact", samples=256, seed=0)
         orders, nll = sample_orders_batch(args, model, enc, samples, seed)
         mode = "uniform"
     else:
-        raise ValueError(f"source must be 'exact', 'nbest' or 'sample', got {source!r}")
+        raise ValueError(f"source must be 'exact', 'nbest', 'sample' or 'tree', got {source!r}")
     post = order_posterior(orders, nll, mode)
     post["orders"], post["nll"] = orders, nll
     return post

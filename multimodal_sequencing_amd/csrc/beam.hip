@@ -21,7 +21,11 @@
 // every slot entered with score 0) and, instead of selecting, adds each slot's own pick to its nll.
 // mmseq_order_sample runs S such slots per story whose pick at every step is DRAWN from the step's
 // distribution (ancestral sampling) with the counter hash of mmseq_mlm_mask.
+// mmseq_order_tree scores ALL N! orders: the prefix tree walked level by level in chunks
+// (order_tree_plan.h), a chunk being a beam of W = nb = cnt slots per story whose children enter
+// with their parent's s entry, so that every shared prefix is stepped once.
 #include "common.h"
+#include "order_tree_plan.h"
 
 namespace {
 
@@ -527,6 +531,128 @@ mmseq_status beam_run(const char* what, int B, int N, int H, int W, const float*
   return MMSEQ_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// mmseq_order_tree: all N! pointer scores from the prefix tree, walked level by level in chunks
+// (order_tree_plan.h). A chunk holds nodes base .. base + cnt - 1 of its level for every story,
+// rows [B][cnt]; every index below follows from the slot index and the chunk's base alone.
+
+// r-th zero bit (ascending) of a mask that has more than r zero bits among its low bits
+__device__ __forceinline__ int tree_nth_free(unsigned pointed, int r) {
+  int j = 0;
+  for (; j < BEAM_MAXN - 1; ++j) {  // bounded whatever the mask holds
+    if ((pointed >> j) & 1u) continue;
+    if (r == 0) break;
+    --r;
+  }
+  return j;
+}
+
+// level 0: row b <- (h0, c0), entering score 0. N == 1: the one order's nll is 0.
+__global__ __launch_bounds__(256) void tree_root_kernel(int N, int H, const float* __restrict__ h0,
+                                                        const float* __restrict__ c0,
+                                                        float* __restrict__ h, float* __restrict__ c,
+                                                        float* __restrict__ score,
+                                                        float* __restrict__ nll) {
+  const int64_t b = blockIdx.x;
+  if (N == 1) {
+    if (threadIdx.x == 0) nll[b] = 0.f;
+    return;
+  }
+  for (int u = threadIdx.x; u < H; u += 256) {
+    h[b * H + u] = h0[b * H + u];
+    c[b * H + u] = c0[b * H + u];
+  }
+  if (threadIdx.x == 0) score[b] = 0.f;
+}
+
+// One workgroup per child slot (story b, node cbase + j of level t, t >= 1 picks made): its parent
+// is node i / (N-t+1) of level t - 1, row b * pcnt + (that - pbase) of the resident parent chunk,
+// and its pick the (i % (N-t+1))-th zero bit of the parent's pointed mask. The child's pick row is
+// the parent's plus the pick, its entering score the parent's s[pick], and its (h, c) the parent's
+// post-step rows (the cell kernel updates in place, so they are copied): 16-byte accesses where
+// H % 4 == 0 (every buffer offset is a multiple of 4 floats), a scalar path otherwise.
+__global__ __launch_bounds__(256) void tree_expand_kernel(int N, int H, int t, int64_t cbase,
+                                                          int64_t ccnt, int64_t pbase, int64_t pcnt,
+                                                          const int* __restrict__ pseq,
+                                                          const float* __restrict__ ps,
+                                                          const float* __restrict__ ph,
+                                                          const float* __restrict__ pc,
+                                                          int* __restrict__ seq,
+                                                          float* __restrict__ score,
+                                                          float* __restrict__ h,
+                                                          float* __restrict__ c) {
+  const int64_t slot = blockIdx.x;
+  const int64_t b = slot / ccnt, i = cbase + slot % ccnt;
+  const int fan = N - t + 1;
+  const int64_t prow = b * pcnt + (i / fan - pbase);
+  const int r = (int)(i % fan);
+  unsigned pointed = 0;
+  for (int p = 0; p < t - 1; ++p) pointed |= 1u << pseq[prow * BEAM_MAXN + p];
+  const int pick = tree_nth_free(pointed, r);
+  if ((int)threadIdx.x < t - 1)
+    seq[slot * BEAM_MAXN + threadIdx.x] = pseq[prow * BEAM_MAXN + threadIdx.x];
+  if (threadIdx.x == 0) {
+    seq[slot * BEAM_MAXN + t - 1] = pick;
+    score[slot] = ps[prow * N + pick];
+  }
+  if ((H & 3) == 0) {
+    const float4* sh = reinterpret_cast<const float4*>(ph + prow * H);
+    const float4* sc = reinterpret_cast<const float4*>(pc + prow * H);
+    float4* dh = reinterpret_cast<float4*>(h + slot * H);
+    float4* dc = reinterpret_cast<float4*>(c + slot * H);
+    for (int u = threadIdx.x; u < H / 4; u += 256) {
+      dh[u] = sh[u];
+      dc[u] = sc[u];
+    }
+  } else {
+    for (int u = threadIdx.x; u < H; u += 256) {
+      h[slot * H + u] = ph[prow * H + u];
+      c[slot * H + u] = pc[prow * H + u];
+    }
+  }
+}
+
+// One thread per slot of a chunk of level N - 2 after its step: the two steps still unpointed,
+// ascending, are the node's children 2i and 2i + 1 of level N - 1, i.e. two lexicographic ranks
+// (N = 2: the root's both picks); their s entries are those orders' nll.
+__global__ __launch_bounds__(256) void tree_leaf_kernel(int64_t R, int N, int64_t base, int64_t cnt,
+                                                        int64_t leaves, const int* __restrict__ seq,
+                                                        const float* __restrict__ s,
+                                                        float* __restrict__ nll) {
+  const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (slot >= R) return;
+  const int64_t b = slot / cnt, i = base + slot % cnt;
+  unsigned pointed = 0;
+  for (int p = 0; p < N - 2; ++p) pointed |= 1u << seq[slot * BEAM_MAXN + p];
+  const int j0 = tree_nth_free(pointed, 0), j1 = tree_nth_free(pointed | (1u << j0), 0);
+  nll[b * leaves + 2 * i] = s[slot * N + j0];
+  nll[b * leaves + 2 * i + 1] = s[slot * N + j1];
+}
+
+// One thread per rank k < N!: the k-th permutation of 0 .. N-1 in lexicographic order, digit p of
+// k in the factorial number system picking the digit-th still-unused value, ascending.
+__global__ __launch_bounds__(256) void tree_unrank_kernel(int64_t leaves, int N,
+                                                          int64_t* __restrict__ orders) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= leaves) return;
+  int64_t f = leaves, rem = k;
+  unsigned used = 0;
+  for (int p = 0; p < N; ++p) {
+    f /= N - p;  // (N - 1 - p)!
+    const int j = tree_nth_free(used, (int)(rem / f));
+    rem %= f;
+    used |= 1u << j;
+    orders[k * N + p] = j;
+  }
+}
+
+inline bool tree_supported(int B, int N, int H) {
+  if (N < 1 || N > order_tree::MAXN || !beam_supported(B, N, H, 1)) return false;
+  int64_t leaves = 1;
+  for (int i = 2; i <= N; ++i) leaves *= i;
+  return (int64_t)B * leaves < INT32_MAX && (int64_t)B * N * 4 * H < INT32_MAX;
+}
+
 }  // namespace
 
 extern "C" int64_t mmseq_beam_workspace(int B, int N, int H, int W) {
@@ -675,4 +801,76 @@ extern "C" mmseq_status mmseq_order_sample(int B, int N, int H, int S, const flo
     if ((e = mmseq_check_launch("sample_pick")) != MMSEQ_OK) return e;
   }
   return MMSEQ_OK;
+}
+
+extern "C" int64_t mmseq_order_tree_workspace(int B, int N, int H, int64_t rows) {
+  order_tree::Plan P;
+  if (!tree_supported(B, N, H) || !order_tree::make_plan(B, N, H, rows, &P)) return 0;
+  return P.total * 4;
+}
+
+extern "C" mmseq_status mmseq_order_tree(int B, int N, int H, const float* doc, const float* okey,
+                                         const float* hist, const float* h0, const float* c0,
+                                         const float* w_ih, const float* b_ih, const float* w_hh,
+                                         const float* b_hh, const float* w_q, const float* b_q,
+                                         const float* w_pw, const float* w_t, const float* b_t,
+                                         int64_t rows, float* nll, int64_t* orders, void* workspace,
+                                         int64_t workspace_bytes, mmseq_stream stream) {
+  if (!tree_supported(B, N, H))
+    return mmseq_set_error(MMSEQ_EUNSUPPORTED,
+                           "order_tree: B=%d N=%d H=%d outside 1 <= N <= %d, B*N! < 2^31, "
+                           "B*N*4H < 2^31 (or B / H beyond the beam's limits)",
+                           B, N, H, order_tree::MAXN);
+  MMSEQ_REQUIRE(doc && okey && hist && h0 && c0 && w_ih && b_ih && w_hh && b_hh && w_q && b_q &&
+                    w_pw && w_t && b_t && nll,
+                "order_tree: null buffer");
+  MMSEQ_REQUIRE(rows >= (int64_t)B * N, "order_tree: rows %lld below B*N = %lld", (long long)rows,
+                (long long)B * N);
+  order_tree::Plan P;
+  MMSEQ_REQUIRE(order_tree::make_plan(B, N, H, rows, &P), "order_tree: no plan for rows %lld",
+                (long long)rows);
+  MMSEQ_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= P.total * 4,
+                "order_tree: workspace must be 16-byte aligned and hold %lld bytes (got %lld)",
+                (long long)(P.total * 4), (long long)workspace_bytes);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  mmseq_status e;
+  if (orders) {
+    hipLaunchKernelGGL(tree_unrank_kernel, dim3((unsigned)((P.leaves + 255) / 256)), dim3(256), 0,
+                       st, P.leaves, N, orders);
+    if ((e = mmseq_check_launch("tree_unrank")) != MMSEQ_OK) return e;
+  }
+  if (B == 0) return MMSEQ_OK;
+  float* ws = reinterpret_cast<float*>(workspace);
+  hipLaunchKernelGGL(tree_root_kernel, dim3(B), dim3(256), 0, st, N, H, h0, c0, ws + P.lv[0].h,
+                     ws + P.lv[0].c, ws + P.lv[0].score, nll);
+  if ((e = mmseq_check_launch("tree_root")) != MMSEQ_OK || N == 1) return e;
+  const BeamWeights wt{w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t};
+  if ((e = beam_story_setup(B, N, H, doc, hist, wt, ws + P.gx, ws + P.proj, P.pstride, stream)) !=
+      MMSEQ_OK)
+    return e;
+  e = MMSEQ_OK;
+  order_tree::walk(P, [&](int t, int64_t base, int64_t cnt, int64_t pbase, int64_t pcnt) {
+    const order_tree::Level& L = P.lv[t];
+    const int R = (int)(B * cnt);
+    int* seq = reinterpret_cast<int*>(ws + L.seq);
+    if (t > 0) {
+      const order_tree::Level& U = P.lv[t - 1];
+      hipLaunchKernelGGL(tree_expand_kernel, dim3(R), dim3(256), 0, st, N, H, t, base, cnt, pbase,
+                         pcnt, reinterpret_cast<const int*>(ws + U.seq), ws + U.s, ws + U.h,
+                         ws + U.c, seq, ws + L.score, ws + L.h, ws + L.c);
+      if ((e = mmseq_check_launch("tree_expand")) != MMSEQ_OK) return false;
+    }
+    // the chunk as a beam of W = nb = cnt live slots per story: slot / cnt is the story
+    if ((e = beam_step(B, N, H, (int)cnt, t, (int)cnt, wt, okey, ws + P.gx, ws + P.proj, P.pstride,
+                       seq, ws + L.score, ws + L.h, ws + L.c, ws + P.gh, ws + P.q, ws + L.s,
+                       stream)) != MMSEQ_OK)
+      return false;
+    if (t == N - 2) {
+      hipLaunchKernelGGL(tree_leaf_kernel, dim3((R + 255) / 256), dim3(256), 0, st, (int64_t)R, N,
+                         base, cnt, P.leaves, seq, ws + L.s, nll);
+      if ((e = mmseq_check_launch("tree_leaf")) != MMSEQ_OK) return false;
+    }
+    return true;
+  });
+  return e;
 }
