@@ -727,6 +727,53 @@ mmseq_status mmseq_order_posterior(int B, int N, int K, int mode, const int64_t*
                                    mmseq_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Decoding from the pairwise head (csrc/pairwise.hip). w [B][N][N] f32, w[a][c] = the log-evidence
+ * that step a precedes step c (berson.pairwise_weights: log_softmax(cs[a][c])[1] +
+ * log_softmax(cs[c][a])[0]; any pairwise score will do); the diagonal is never read. For an order
+ * o (o[t] = the step at position t)
+ *   G(o) = sum_{i<j} w[o_i][o_j],  pnll(o) = -G(o),  Q(o) = exp(G(o)) / Z.
+ * mmseq_pairwise_order: the arg-max of G and the distribution Q, exactly, by dynamic programming
+ * over the 2^N subsets S of steps already placed; one workgroup per story, f64 throughout.
+ *   g(S, c)   = sum_{a in S} w[a][c], a ascending, from 0.0
+ *   h1[full] = 0, h2[full] = -inf; below full {h1[S], h2[S]} = the two largest of
+ *               {g(S,c) + h1[S+c], g(S,c) + h2[S+c] : c not in S}: the best and second-best
+ *               completion as distinct orders (equal values give h2 = h1)
+ *   order     [B][N] int64: from the front, the lowest c not in S with g(S,c) + h1[S+c] == h1[S]:
+ *               the lexicographically smallest maximiser
+ *   pnll      [B] f32(-h1[0]);  margin [B] f32(h1[0] - h2[0]), +inf for N = 1
+ *   la[0] = 0, la[T] = log sum_{c in T} exp(la[T-c] + g(T-c, c));  lb[full] = 0,
+ *   lb[S] = log sum_{c not in S} exp(g(S,c) + lb[S+c]): each c ascending, shifted by its largest
+ *               term
+ *   logz      [B] la[full]
+ *   p(S, c)   = exp(((la[S] + g(S,c)) + lb[S+c]) - logz)
+ *   position  [B][N][N]: position[t][s] = sum_{|S| = t, s not in S} p(S, s)
+ *   before    [B][N][N]: before[a][c] = sum_{S has a, not c} p(S, c); diagonal 0; both S ascending
+ *   entropy   [B] logz - sum_{a != c} before[a][c] w[a][c], (a, c) lexicographic, from the f64 sums
+ * Every output is rounded once to f32. No atomics: bit-identical between calls and independent of
+ * B and of which stories share the launch. A story with a non-finite off-diagonal w gets order -1,
+ * pnll +inf, margin 0, logz -inf, zero matrices and entropy 0.
+ *   workspace  mmseq_pairwise_order_workspace(B, N) bytes (a positive multiple of 16 for a
+ *              supported shape, 0 otherwise), 16-byte aligned, contents irrelevant on entry: the
+ *              tables of N = 12; up to N = 11 they live in LDS and it is not touched.
+ * Supported: B >= 0, 1 <= N <= 12, else MMSEQ_EUNSUPPORTED with nothing launched or written; a
+ * null buffer or a short / unaligned workspace MMSEQ_EINVAL, likewise.
+ * mmseq_pairwise_score: pnll[b][k] = f32(-sum_{i<j} w[b][o_i][o_j]), (i, j) lexicographic, in
+ * f64, of candidate k of story b at orders + b * story_stride + k * N (story_stride = 0: one list
+ * [K][N] for all stories; >= K * N: per story), as mmseq_order_posterior. A candidate that is no
+ * permutation of 0 .. N-1 (checked before any entry is used as an index) gets +inf, and so does
+ * every candidate of a story with a non-finite off-diagonal w.
+ * Supported: B >= 0, 1 <= N <= 16, K >= 1, else MMSEQ_EUNSUPPORTED with nothing launched; a null
+ * buffer or a story_stride that is neither 0 nor >= K * N MMSEQ_EINVAL.
+ * ------------------------------------------------------------------------------------------ */
+int64_t mmseq_pairwise_order_workspace(int B, int N);
+mmseq_status mmseq_pairwise_order(int B, int N, const float* w, int64_t* order, float* pnll,
+                                  float* margin, float* logz, float* position, float* before,
+                                  float* entropy, void* workspace, int64_t workspace_bytes,
+                                  mmseq_stream stream);
+mmseq_status mmseq_pairwise_score(int B, int N, int K, const float* w, const int64_t* orders,
+                                  int64_t story_stride, float* pnll, mmseq_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * MX-fp8 forward GEMMs (BASELINE config 5 "fp8 MFMA"; v_mfma_scale_f32_16x16x128_f8f6f4).
  *  Format: OCP e4m3 elements, one E8M0 scale (2^(s-127)) per 32 consecutive K-elements of a row
  *  (OCP MX: s = floor(log2 amax) - 8 + 127, elements = x / 2^(s-127) clamped to +-448, RNE).

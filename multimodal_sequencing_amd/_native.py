@@ -167,6 +167,9 @@ _SIGS = {
                            [_vp] * 5 + [_c_i64, _vp]),
     "mmseq_order_posterior": (ctypes.c_int, [ctypes.c_int] * 4 + [_vp, _c_i64] + [_vp] * 11 +
                               [_vp]),
+    "mmseq_pairwise_order_workspace": (ctypes.c_int64, [ctypes.c_int] * 2),
+    "mmseq_pairwise_order": (ctypes.c_int, [ctypes.c_int] * 2 + [_vp] * 9 + [_c_i64, _vp]),
+    "mmseq_pairwise_score": (ctypes.c_int, [ctypes.c_int] * 3 + [_vp, _vp, _c_i64, _vp, _vp]),
     "mmseq_order_tree_workspace": (ctypes.c_int64, [ctypes.c_int] * 3 + [_c_i64]),
     "mmseq_order_tree": (ctypes.c_int, [ctypes.c_int] * 3 + [_vp] * 14 + [_c_i64] + [_vp] * 3 +
                          [_c_i64, _vp]),
@@ -836,6 +839,63 @@ def order_posterior(orders, nll, mode, out):
                                      _stream())
     if st != EUNSUPPORTED:
         _check(st, "mmseq_order_posterior")
+    return st
+
+
+# name -> (dtype, trailing shape in units of N) of mmseq_pairwise_order's outputs, in ABI order
+PAIRWISE_OUTPUTS = (("order", torch.int64, 1), ("pnll", torch.float32, 0),
+                    ("margin", torch.float32, 0), ("logz", torch.float32, 0),
+                    ("position", torch.float32, 2), ("before", torch.float32, 2),
+                    ("entropy", torch.float32, 0))
+
+
+def pairwise_order_workspace(B, N):
+    """Bytes of workspace mmseq_pairwise_order needs; 0 where the shape is unsupported."""
+    return int(lib().mmseq_pairwise_order_workspace(B, N))
+
+
+def pairwise_order(w, out, workspace):
+    """mmseq_pairwise_order: w f32 [B][N][N]; out: dict name -> contiguous device tensor for every
+    entry of PAIRWISE_OUTPUTS ([B], [B][N] for the order, [B][N][N] for the two matrices);
+    workspace of at least pairwise_order_workspace(B, N) bytes. Returns the status for
+    MMSEQ_EUNSUPPORTED and raises on every other failure."""
+    if w.dim() != 3 or w.shape[1] != w.shape[2]:
+        raise ValueError(f"pairwise_order: w must be [B][N][N], got {tuple(w.shape)}")
+    B, N = int(w.shape[0]), int(w.shape[1])
+    checks = [(w, torch.float32, (B, N, N))]
+    for name, dtype, nn in PAIRWISE_OUTPUTS:
+        checks.append((out[name], dtype, (B,) + (N,) * nn))
+    _dev(*(t for t, _, _ in checks))
+    for t, dtype, shp in checks:
+        if t.dtype != dtype or tuple(t.shape) != shp or not t.is_contiguous():
+            raise ValueError(f"pairwise_order: contiguous {dtype} {shp} expected, got "
+                             f"{tuple(t.shape)} {t.dtype}")
+    st = lib().mmseq_pairwise_order(B, N, _p(w), *(_p(out[name]) for name, _, _ in PAIRWISE_OUTPUTS),
+                                    _p(workspace), _ws_bytes(workspace), _stream())
+    if st != EUNSUPPORTED:
+        _check(st, "mmseq_pairwise_order")
+    return st
+
+
+def pairwise_score(w, orders, pnll):
+    """mmseq_pairwise_score: w f32 [B][N][N], orders int64 [K][N] or [B][K][N], pnll f32 [B][K].
+    Returns the status for MMSEQ_EUNSUPPORTED and raises on every other failure."""
+    if w.dim() != 3 or w.shape[1] != w.shape[2] or orders.dim() not in (2, 3):
+        raise ValueError("pairwise_score: w must be [B][N][N], orders [K][N] or [B][K][N]")
+    B, N = int(w.shape[0]), int(w.shape[1])
+    K = int(orders.shape[-2])
+    oshape = (K, N) if orders.dim() == 2 else (B, K, N)
+    checks = [(w, torch.float32, (B, N, N)), (orders, torch.int64, oshape),
+              (pnll, torch.float32, (B, K))]
+    _dev(*(t for t, _, _ in checks))
+    for t, dtype, shp in checks:
+        if t.dtype != dtype or tuple(t.shape) != shp or not t.is_contiguous():
+            raise ValueError(f"pairwise_score: contiguous {dtype} {shp} expected, got "
+                             f"{tuple(t.shape)} {t.dtype}")
+    st = lib().mmseq_pairwise_score(B, N, K, _p(w), _p(orders),
+                                    0 if orders.dim() == 2 else K * N, _p(pnll), _stream())
+    if st != EUNSUPPORTED:
+        _check(st, "mmseq_pairwise_score")
     return st
 
 

@@ -486,10 +486,14 @@ def berson_pointer_network_batch(args, model, tokenizer, inputs, decode="beam", 
     enumeration (default args.order_enumeration, else "flat") says how all N! orders are scored:
     "flat" as above; "tree": through the prefix tree (enumerate_orders_batch), which carries
     decode="exact" and the exact posterior of "mbr_*" up to N = TREE_MAX_N = 9; above that "exact"
-    raises and "mbr_*" samples as with "flat"."""
-    if decode not in ("beam", "exact", "mbr_acc", "mbr_tau"):
-        raise ValueError("decode must be 'beam', 'exact', 'mbr_acc' or 'mbr_tau', "
-                         f"got {decode!r}")
+    raises and "mbr_*" samples as with "flat".
+    decode="pairwise": the exact optimum of the pairwise head (pairwise_order_batch, N <= 12);
+    `model.last_beam_scores` then holds its pnll. decode="joint": the arg-min over all N! orders
+    of the model's own training loss J (joint_order_batch), enumerated as for "exact";
+    `model.last_beam_scores` then holds J."""
+    if decode not in ("beam", "exact", "mbr_acc", "mbr_tau", "pairwise", "joint"):
+        raise ValueError("decode must be 'beam', 'exact', 'mbr_acc' or 'mbr_tau', 'pairwise' or "
+                         f"'joint', got {decode!r}")
     if enumeration is None:
         enumeration = getattr(args, "order_enumeration", "flat")
     if enumeration not in ("flat", "tree"):
@@ -502,6 +506,14 @@ def berson_pointer_network_batch(args, model, tokenizer, inputs, decode="beam", 
         enc = model.encode(**berson)
         if decode == "exact":
             order, model.last_beam_scores, _ = exact_order_batch(
+                args, model, enc, method="tree" if tree else "flat")
+            return order.tolist()
+        if decode == "pairwise":
+            post = pairwise_order_batch(args, model, enc)
+            model.last_beam_scores = post["pnll"]
+            return post["order"].tolist()
+        if decode == "joint":
+            order, model.last_beam_scores, _ = joint_order_batch(
                 args, model, enc, method="tree" if tree else "flat")
             return order.tolist()
         N = enc[0].shape[1]
@@ -947,3 +959,140 @@ def berson_order_posterior(args, model, tokenizer, inputs, source="exact", sampl
     with torch.no_grad():
         enc = model.encode(**_batch_inputs(model, inputs))
         return order_posterior_batch(args, model, enc, source, samples, seed)
+
+
+# ------------------------------------------------------------------------------------------------
+# Decoding from the pairwise head, joint decode.
+PAIRWISE_MAX_N = 12  # 2^12 = 4096 subsets per story (mmseq_pairwise_order)
+
+
+@torch.no_grad()
+def pairwise_weights(cs_mat):
+    """cs_mat f32 [B][N][N][2] (enc[7]: the pairwise head's logits for "a before c" at [a][c]) ->
+    w f32 [B][N][N], w[a][c] = log_softmax(cs[a][c])[1] + log_softmax(cs[c][a])[0]: the
+    log-evidence of both pair views that a precedes c; diagonal 0. For an order o,
+    pnll(o) = -sum_{i<j} w[o_i][o_j] is the numerator of the pairwise training loss with the
+    labels o implies."""
+    if cs_mat.dim() != 4 or cs_mat.shape[1] != cs_mat.shape[2] or cs_mat.shape[3] != 2:
+        raise ValueError(f"cs_mat must be [B][N][N][2], got {tuple(cs_mat.shape)}")
+    ls = torch.log_softmax(cs_mat.float(), -1)
+    w = ls[..., 1] + ls[..., 0].transpose(1, 2)
+    eye = torch.eye(cs_mat.shape[1], dtype=torch.bool, device=cs_mat.device)
+    return w.masked_fill(eye[None], 0.0).contiguous()
+
+
+@torch.no_grad()
+def pairwise_order_batch(args, model, enc):
+    """The pairwise head's own decode for every story of an encode() tuple, exactly, through ONE
+    mmseq_pairwise_order (a DP over the 2^N subsets, not over N!) -> dict of device tensors:
+    order int64 [B][N] (the arg-min of pnll, ties to the lexicographically smallest), pnll, margin
+    (runner-up minus best), logz, entropy f32 [B] and position, before f32 [B][N][N], the exact
+    marginals of Q(o) ~ exp(-pnll(o)) (order_posterior_batch's key names where the meanings
+    coincide), plus "w", the weights they were taken over. N <= PAIRWISE_MAX_N = 12; ValueError
+    above. Nothing synchronises; the workspace is cached on the model like the beam's."""
+    w = pairwise_weights(enc[7])
+    B, N = int(w.shape[0]), int(w.shape[1])
+    if N > PAIRWISE_MAX_N:
+        raise ValueError(f"pairwise_order_batch walks all 2^N subsets: N = {N} exceeds "
+                         f"{PAIRWISE_MAX_N}")
+    dev = w.device
+    out = {name: torch.empty((B,) + (N,) * nn, dtype=dtype, device=dev)
+           for name, dtype, nn in N_.PAIRWISE_OUTPUTS}
+    nbytes = N_.pairwise_order_workspace(B, N)
+    if nbytes == 0:
+        raise N_.Unsupported(f"pairwise_order_batch: B={B} N={N} is outside "
+                             "mmseq_pairwise_order's limits")
+    cache = model.__dict__.setdefault("_pairwise_ws", {})
+    ws = cache.get((B, N))
+    if ws is None:
+        ws = cache[(B, N)] = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    N_._check_shape(N_.pairwise_order(w, out, ws), "mmseq_pairwise_order")
+    out["w"] = w
+    return out
+
+
+@torch.no_grad()
+def pairwise_score_orders(args, model, enc, orders):
+    """pnll of K candidate orders under the pairwise head for every story of an encode() tuple
+    (mmseq_pairwise_score) -> f32 [B][K] on the device. `orders` as for score_orders_batch: a
+    list or CPU tensor is validated here (check_orders); a device tensor is not synchronised on,
+    and a candidate in it that is no permutation comes back as +inf. N > 16 raises
+    _native.Unsupported."""
+    w = pairwise_weights(enc[7])
+    B, N = int(w.shape[0]), int(w.shape[1])
+    if torch.is_tensor(orders) and orders.is_cuda:
+        o = orders
+        if o.dtype != torch.int64 or o.dim() not in (2, 3) or o.shape[-1] != N or \
+                o.shape[-2] < 1 or (o.dim() == 3 and o.shape[0] != B):
+            raise ValueError(f"orders must be int64 [K][{N}] or [{B}][K][{N}] with K >= 1, got "
+                             f"{o.dtype} {tuple(o.shape)}")
+        o = o.contiguous()
+    else:
+        o = check_orders(orders, B, N).to(w.device)
+    pnll = torch.empty(B, int(o.shape[-2]), dtype=torch.float32, device=w.device)
+    N_._check_shape(N_.pairwise_score(w, o, pnll), "mmseq_pairwise_score")
+    return pnll
+
+
+@torch.no_grad()
+def joint_order_batch(args, model, enc, lam=None, method="flat"):
+    """The order under which the model's own training loss is smallest, for every story of an
+    encode() tuple: the arg-min over ALL N! orders (itertools.permutations order, ties to the
+    lowest index) of J(o) = nll_ptr(o) / (N - 1) + lam * pnll(o) / (N (N - 1)), what
+    `model({**inputs, "labels": o})` would report for that story -> (order int64 [B][N], J f32
+    [B], margin f32 [B]) on the device. lam defaults to model.pairwise_loss_lam. The pointer part
+    comes from score_orders_batch (method="flat", N <= 7) or enumerate_orders_batch ("tree",
+    N <= 9), the pairwise part from pairwise_score_orders on the same list."""
+    import itertools
+    if method not in ("flat", "tree"):
+        raise ValueError(f"method must be 'flat' or 'tree', got {method!r}")
+    B, N, _H = enc[0].shape
+    lam = float(model.pairwise_loss_lam if lam is None else lam)
+    if method == "tree":
+        if N > TREE_MAX_N:
+            raise ValueError(f"joint_order_batch(method='tree') enumerates N! orders: N = {N} "
+                             f"exceeds {TREE_MAX_N}")
+        nll, perms = enumerate_orders_batch(args, model, enc, return_orders=True)
+    else:
+        if N > EXACT_MAX_N:
+            raise ValueError(f"joint_order_batch enumerates N! orders: N = {N} exceeds "
+                             f"{EXACT_MAX_N}")
+        perms = torch.tensor(list(itertools.permutations(range(N))), dtype=torch.int64,
+                             device=enc[0].device)
+        nll = score_orders_batch(args, model, enc, perms)
+    pnll = pairwise_score_orders(args, model, enc, perms)
+    J = nll / max(N - 1, 1) + pnll * (lam / max(N * (N - 1), 1))
+    idx, best, margin = exact_from_scores(J)
+    return perms[idx], best, margin
+
+
+def topological_order_host(w):
+    """The legacy pairwise decode (trainers/eval.py topological_inference), restated for
+    comparison: hard decisions, then a depth-first topological sort. w: [N][N] host values (lists,
+    numpy or a CPU tensor) -> list of N steps. Edge a -> c where w[a][c] > w[c][a] (from the lower
+    to the higher index where they are equal); every vertex's successors in ascending order;
+    depth-first from vertex 0, 1, .. with no asserted head, a vertex going to the FRONT of the
+    result when its successors are done. On a cyclic tournament the result depends on the
+    traversal order alone."""
+    w = [[float(x) for x in row] for row in w]
+    N = len(w)
+    succ = [[] for _ in range(N)]
+    for a in range(N):
+        for c in range(a + 1, N):
+            if w[a][c] >= w[c][a]:
+                succ[a].append(c)
+            else:
+                succ[c].append(a)
+    seen, done = [False] * N, []
+
+    def visit(v):
+        seen[v] = True
+        for u in succ[v]:
+            if not seen[u]:
+                visit(u)
+        done.append(v)
+
+    for v in range(N):
+        if not seen[v]:
+            visit(v)
+    return done[::-1]
