@@ -602,6 +602,50 @@ mmseq_status mmseq_order_score(int B, int N, int H, int K, const float* doc, con
                                mmseq_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Gradient of mmseq_order_score: given dnll[b][k], the upstream gradient of every score, the
+ * gradients with respect to the encoder output and the decoder weights, for sequence-level losses
+ * over a candidate list (expected risk, likelihood of a set of orders, margins). The ABI keeps no
+ * state between calls: this entry recomputes the scorer's forward (its own kernels, the scorer's
+ * formulation: GX and the four projected blocks of hist once per story, K slots that never
+ * branch), keeps h_t, c_t and the gate activations of every step in its workspace and walks
+ * t = N-2 .. 0. With y_t = orders[k][t], S_t = {y_0 .. y_{t-1}}, G = dnll[b][k]:
+ *   de_t[j]   = G (p_t[j] - [j = y_t]) for j not in S_t, exactly 0 for j in S_t
+ *   dA_t[j]   = de_t[j] w_t (1 - a_t[j]^2),  dq_t = sum_j dA_t[j] (j ascending)
+ *   dh_t      = W_hh^T dgates_{t+1} + W_q^T dq_t, then mmseq_lstm_cell_bwd's math on B*K rows
+ *   dh0 / dc0 = the slots' sums, k ascending
+ * Reductions to per-story rows (dGX, dokey, the four dPROJ blocks) are gathers: one workgroup per
+ * destination row loops k ascending, then t ascending. No atomics; two calls on the same inputs
+ * give bit-identical outputs. The dense parts run through mmseq_gemm / mmseq_gemm_wgrad in fp32.
+ *   doc .. b_t, orders, story_stride   as mmseq_order_score
+ *   wt_ih, wt_hh [H][4H], wt_q [H][H], wt_pw [4(H+2)][H]   the weights transposed, [in][out]
+ *   dnll         [B][K] f32
+ *   WRITTEN      ddoc, dokey [B][N][H], dhist [B][N][N][H+2], dh0, dc0 [B][H]
+ *   ACCUMULATED  (+=) dw_ih, db_ih, dw_hh, db_hh, dw_q, db_q, dw_pw, dw_t, db_t, shaped as the
+ *                weights
+ * An invalid candidate (checked before any entry forms an address, as in mmseq_order_score)
+ * contributes exactly zero whatever its dnll holds, NaN included. N = 1: the written gradients are
+ * zeros, the accumulated ones untouched, nothing else is launched. N = 2: a single step with
+ * x = 0, so ddoc = 0 and dw_ih is unchanged (db_ih is not: b_ih enters step 0).
+ * Limits and status codes as mmseq_order_score (MMSEQ_EUNSUPPORTED before anything is launched;
+ * a null buffer, a bad story_stride or a short / unaligned workspace MMSEQ_EINVAL).
+ *   workspace: mmseq_order_score_bwd_workspace(B, N, H, K) bytes (0 for an unsupported shape),
+ *     16-byte aligned, contents irrelevant on entry (NaN in it reaches no output). It holds
+ *     about (N-1) B K (N+8) H floats of per-step state, so callers chunk K. Nothing is written outside
+ *     the fourteen gradients and the workspace.
+ * Stream ordering as for mmseq_beam_search.
+ * ------------------------------------------------------------------------------------------ */
+int64_t mmseq_order_score_bwd_workspace(int B, int N, int H, int K);
+mmseq_status mmseq_order_score_bwd(
+    int B, int N, int H, int K, const float* doc, const float* okey, const float* hist,
+    const float* h0, const float* c0, const float* w_ih, const float* b_ih, const float* w_hh,
+    const float* b_hh, const float* w_q, const float* b_q, const float* w_pw, const float* w_t,
+    const float* b_t, const float* wt_ih, const float* wt_hh, const float* wt_q, const float* wt_pw,
+    const int64_t* orders, int64_t story_stride, const float* dnll, float* ddoc, float* dokey,
+    float* dhist, float* dh0, float* dc0, float* dw_ih, float* db_ih, float* dw_hh, float* db_hh,
+    float* dw_q, float* db_q, float* dw_pw, float* dw_t, float* db_t, void* workspace,
+    int64_t workspace_bytes, mmseq_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Ancestral samples from the pointer decoder: S orders per story drawn step by step from the
  * distributions mmseq_order_score scores. Sample s of story b is a beam slot that never branches
  * (the setup, the step and the kernels of mmseq_beam_search; W = nb = S, every step entered with

@@ -161,6 +161,9 @@ _SIGS = {
     "mmseq_order_score_workspace": (ctypes.c_int64, [ctypes.c_int] * 4),
     "mmseq_order_score": (ctypes.c_int, [ctypes.c_int] * 4 + [_vp] * 15 + [_c_i64] +
                           [_vp] * 3 + [_c_i64, _vp]),
+    "mmseq_order_score_bwd_workspace": (ctypes.c_int64, [ctypes.c_int] * 4),
+    "mmseq_order_score_bwd": (ctypes.c_int, [ctypes.c_int] * 4 + [_vp] * 19 + [_c_i64] +
+                              [_vp] * 16 + [_c_i64, _vp]),
     "mmseq_order_sample_workspace": (ctypes.c_int64, [ctypes.c_int] * 4),
     "mmseq_order_sample": (ctypes.c_int, [ctypes.c_int] * 4 + [_vp] * 14 +
                            [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_int] +
@@ -748,6 +751,49 @@ def order_score(doc, okey, hist, h0, c0, weights, orders, nll, step_nll, workspa
                                  _p(workspace), _ws_bytes(workspace), _stream())
     if st != EUNSUPPORTED:
         _check(st, "mmseq_order_score")
+    return st
+
+
+def order_score_bwd_workspace(B, N, H, K):
+    """Bytes of workspace mmseq_order_score_bwd needs; 0 where the shape is unsupported."""
+    return int(lib().mmseq_order_score_bwd_workspace(B, N, H, K))
+
+
+def order_score_bwd(doc, okey, hist, h0, c0, weights, weights_t, orders, dnll, dins, dweights,
+                    workspace):
+    """mmseq_order_score_bwd: the inputs of order_score; weights_t = (wt_ih, wt_hh, wt_q, wt_pw),
+    the [in][out] copies; dnll f32 [B][K]; dins = (ddoc, dokey, dhist, dh0, dc0), WRITTEN;
+    dweights = the nine weight gradients in the order of `weights`, ACCUMULATED (+=); workspace of
+    at least order_score_bwd_workspace(B, N, H, K) bytes. Returns the status for
+    MMSEQ_EUNSUPPORTED and raises on every other failure."""
+    B, N, H = doc.shape
+    if orders.dim() not in (2, 3):
+        raise ValueError("order_score_bwd: orders must be int64 [K][N] or [B][K][N]")
+    K = int(orders.shape[-2])
+    oshape = (K, N) if orders.dim() == 2 else (B, K, N)
+    if len(weights_t) != 4 or len(dins) != 5 or len(dweights) != 9:
+        raise ValueError("order_score_bwd: 4 transposed weights, 5 input and 9 weight gradients "
+                         "expected")
+    ddoc, dokey, dhist, dh0, dc0 = dins
+    f32 = torch.float32
+    extra = [(orders, torch.int64, oshape), (dnll, f32, (B, K)), (ddoc, f32, (B, N, H)),
+             (dokey, f32, (B, N, H)), (dhist, f32, (B, N, N, H + 2)), (dh0, f32, (B, H)),
+             (dc0, f32, (B, H))]
+    for t, shp in zip(weights_t, ((H, 4 * H), (H, 4 * H), (H, H), (4 * (H + 2), H))):
+        extra.append((t, f32, shp))
+    for g, w in zip(dweights[:7], weights[:7]):
+        extra.append((g, f32, tuple(w.shape)))
+    for g, n in zip(dweights[7:], (H, 1)):
+        if g.dtype != f32 or g.numel() != n or not g.is_contiguous():
+            raise ValueError("order_score_bwd: tanh_linear gradients [H] / [1] f32 expected")
+    _dev(*dweights[7:])
+    ptrs = _beam_inputs("order_score_bwd", doc, okey, hist, h0, c0, weights, extra)
+    st = lib().mmseq_order_score_bwd(B, N, H, K, *ptrs, *[_p(t) for t in weights_t], _p(orders),
+                                     0 if orders.dim() == 2 else K * N, _p(dnll),
+                                     *[_p(t) for t in dins], *[_p(t) for t in dweights],
+                                     _p(workspace), _ws_bytes(workspace), _stream())
+    if st != EUNSUPPORTED:
+        _check(st, "mmseq_order_score_bwd")
     return st
 
 

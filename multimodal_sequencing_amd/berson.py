@@ -688,6 +688,200 @@ def berson_score_orders(args, model, tokenizer, inputs, orders, return_steps=Fal
         return score_orders_batch(args, model, enc, orders, return_steps)
 
 
+# ------------------------------------------------------------------------------------------------
+# Gradients of candidate-order scores and sequence-level losses.
+def _device_orders(orders, B, N, dev):
+    """score_orders_batch's handling of `orders`: a device tensor is checked for shape only (no
+    synchronisation), anything else is validated on the host and copied."""
+    if torch.is_tensor(orders) and orders.is_cuda:
+        o = orders
+        if o.dtype != torch.int64 or o.dim() not in (2, 3) or o.shape[-1] != N or \
+                o.shape[-2] < 1 or (o.dim() == 3 and o.shape[0] != B):
+            raise ValueError(f"orders must be int64 [K][{N}] or [{B}][K][{N}] with K >= 1, got "
+                             f"{o.dtype} {tuple(o.shape)}")
+        return o
+    return check_orders(orders, B, N).to(dev)
+
+
+def score_orders_grad(args, model, enc, orders):
+    """score_orders_batch with a graph: nll f32 [B][K] of K candidate orders per story, attached
+    to the graph of the encode() tuple `enc` (K.OrderScoreFn: mmseq_order_score forward, the same
+    bits as score_orders_batch, mmseq_order_score_bwd backward). Gradients reach the encoder
+    through doc, okey, cls_mat, cs_mat and the decoder's initial state, and the nine decoder
+    weights through the head store. `orders` as for score_orders_batch; a candidate of a device
+    tensor that is no permutation scores +inf and contributes no gradient. K is chunked so that
+    the backward workspace stays within SCORE_WS_CAP. Where the ABI reports the shape unsupported
+    (N > 16) the candidates go through score_orders_autograd."""
+    (sent, _p, dec_init, okeys, _cls, cls_mat, _cs, cs_mat, _h1, _h2) = enc
+    B, N, H = sent.shape
+    o = _device_orders(orders, B, N, sent.device)
+    if K.order_grad_chunk(B, N, H, int(o.shape[-2]), SCORE_WS_CAP)[1] == 0:
+        return score_orders_autograd(args, model, enc, o)
+    hist = torch.cat([cls_mat, torch.softmax(cs_mat, -1)], -1)
+    return K.OrderScoreFn.apply(sent, okeys, hist, dec_init[0][0], dec_init[1][0], model._anchor,
+                                model.store, o, SCORE_WS_CAP)
+
+
+def score_orders_autograd(args, model, enc, orders):
+    """The value and the gradients of score_orders_grad in torch only: the encoder output tiled K
+    times through the training decoder's own Functions (LinearFn, LstmCellFn, PointerFn), i.e.
+    _forward's pointer loop on B*K rows with labels = the candidates. It materialises
+    [B*K][N][N][N][H+2] and projects hist once per (candidate, step, key): the fallback where
+    mmseq_order_score_bwd reports the shape unsupported, and the cross-check of the tests. The
+    candidates are validated on the host (a device tensor is copied there)."""
+    (sent, _p, dec_init, okeys, _cls, cls_mat, _cs, cs_mat, _h1, _h2) = enc
+    B, N, H = sent.shape
+    dev = sent.device
+    o = check_orders(orders.cpu() if torch.is_tensor(orders) else orders, B, N).to(dev)
+    Kn = int(o.shape[-2])
+    if N == 1:
+        return sent.new_zeros(B, Kn) + 0.0 * sent.sum()
+    target = (o[None].expand(B, -1, -1) if o.dim() == 2 else o).reshape(B * Kn, N)
+    R = B * Kn
+
+    def tile(x):
+        return x[:, None].expand(B, Kn, *x.shape[1:]).reshape(R, *x.shape[1:])
+
+    doc, okey = tile(sent), tile(okeys)
+    hist = tile(torch.cat([cls_mat, torch.softmax(cs_mat, -1)], -1))
+    ar = torch.arange(N, device=dev)
+    onehot = F.one_hot(target, N).to(torch.int64)
+    pointed = (onehot.cumsum(1) - onehot).clamp_(max=1)
+    base = (1 - torch.eye(N, dtype=torch.int64, device=dev))[None]
+    alive = 1 - pointed
+    rela_mask = base[:, None] * alive[:, :, :, None] * alive[:, :, None, :]
+    live = hist[:, None] * rela_mask[..., None].to(hist.dtype)
+    forw, back = live.mean(3), live.mean(2)
+    ridx = torch.arange(R, device=dev)[:, None]
+    prev1 = torch.cat([target.new_zeros(R, 1), target[:, :-1]], 1)
+    prev2 = torch.cat([target.new_zeros(R, 2), target[:, :-2]], 1)[:, :N]
+    l1 = hist[ridx, prev1] * (ar >= 1).to(hist.dtype)[None, :, None, None]
+    l2 = hist[ridx, prev2] * (ar >= 2).to(hist.dtype)[None, :, None, None]
+    pw_keys = K.LinearFn.apply(torch.cat([l1, l2, forw, back], -1), model._anchor, model.store,
+                               "pw_k.weight", None, 0)
+    dec_in = torch.cat([doc.new_zeros(R, 1, H), doc[ridx, target[:, :-1]]], 1)
+    h, c = tile(dec_init[0][0]), tile(dec_init[1][0])
+    gx = model._lstm_gx(dec_in)
+    outs = []
+    for t in range(N):
+        h, c = model._lstm_step(gx[:, t], h, c)
+        outs.append(h)
+    query = model._lin(torch.stack(outs, 1), "query_linear")
+    tgt_len = torch.full((R,), N, dtype=torch.int64, device=dev)
+    nll, _logp = K.PointerFn.apply(query, pw_keys, okey, model._anchor, model.store,
+                                   "tanh_linear.weight", "tanh_linear.bias",
+                                   pointed.to(torch.uint8).contiguous(), tgt_len, target.contiguous())
+    return nll[:, :N - 1].sum(-1).view(B, Kn)
+
+
+def order_gains(orders, gold, metric="tau"):
+    """Per-candidate gain of orders int64 [K][N] or [B][K][N] against gold [B][N] -> f32 [B][K]:
+    metric="acc" the share of positions that agree, "tau" Kendall's tau, both as
+    evaluate.cal_result computes them per story (and as mmseq_order_posterior's gain_acc /
+    gain_tau against a posterior that is a point mass on gold). N = 1: 1. A candidate that is no
+    permutation gets some finite value; it is meant to weigh 0."""
+    if metric not in ("tau", "acc"):
+        raise ValueError(f"metric must be 'tau' or 'acc', got {metric!r}")
+    B, N = gold.shape
+    o = orders[None].expand(B, -1, -1) if orders.dim() == 2 else orders
+    if metric == "acc":
+        return (o == gold[:, None]).float().mean(-1)
+    if N == 1:
+        return torch.ones(o.shape[:2], dtype=torch.float32, device=gold.device)
+    pos_o = o.clamp(0, N - 1).argsort(-1)  # position of every sentence in the candidate
+    pos_g = gold.argsort(-1)[:, None]
+    so = torch.sign(pos_o[..., :, None] - pos_o[..., None, :])
+    sg = torch.sign(pos_g[..., :, None] - pos_g[..., None, :])
+    upper = torch.triu(torch.ones(N, N, dtype=torch.bool, device=gold.device), 1)
+    disc = ((so != sg) & upper).sum((-1, -2)).float()
+    return 1.0 - 2.0 * disc / (N * (N - 1) / 2)
+
+
+def order_loss(nll, orders, gold, kind, metric="tau", alpha=1.0, margin=1.0, refs=None):
+    """A sequence-level loss over scored candidates, pure torch on nll [B][K] (differentiable),
+    mean over stories. orders int64 [K][N] or [B][K][N], gold int64 [B][N].
+      "risk":    sum_k softmax_k(-alpha nll) (1 - gain(order_k, gold)), gain by `metric`
+                 (order_gains); a +inf score weighs 0.
+      "set_nll": -logsumexp_{k in refs}(-nll_k) / (N - 1), the likelihood of a set of acceptable
+                 orders; refs bool [B][K], by default the candidates equal to gold. Every story
+                 needs at least one.
+      "margin":  relu(margin + nll_gold - min_{k wrong} nll_k) / (N - 1), nll_gold the best score
+                 in refs and wrong the candidates outside refs; 0 where there is no wrong one.
+                 margin = 1.0 is the value of the reference's own ranking losses."""
+    B, N = gold.shape
+    if kind == "risk":
+        w = torch.softmax(-alpha * nll, -1)
+        return (w * (1.0 - order_gains(orders, gold, metric))).sum(-1).mean()
+    if kind not in ("set_nll", "margin"):
+        raise ValueError(f"kind must be 'risk', 'set_nll' or 'margin', got {kind!r}")
+    if refs is None:
+        o = orders[None].expand(B, -1, -1) if orders.dim() == 2 else orders
+        refs = (o == gold[:, None]).all(-1)
+    steps = max(N - 1, 1)
+    inf = float("inf")
+    if kind == "set_nll":
+        return (-torch.logsumexp((-nll).masked_fill(~refs, -inf), -1) / steps).mean()
+    right = nll.masked_fill(~refs, inf).amin(-1)
+    wrong = nll.masked_fill(refs, inf).amin(-1)
+    return (torch.relu(margin + right - wrong) / steps).mean()
+
+
+def _candidate_set(orders):
+    """orders int64 [B][K][N]: every row equal to an earlier row of its story becomes -1 (no
+    permutation: it scores +inf and contributes no gradient), so the list is a set."""
+    same = (orders[:, :, None] == orders[:, None, :]).all(-1)  # [B][K][K]
+    Kn = orders.shape[1]
+    earlier = torch.tril(torch.ones(Kn, Kn, dtype=torch.bool, device=orders.device), -1)
+    dup = (same & earlier).any(-1)
+    return torch.where(dup[..., None], torch.full_like(orders, -1), orders)
+
+
+def sequence_loss(args, model, inputs, objective="risk", candidates="sample", samples=16, seed=0,
+                  seq_lam=1.0, **loss_kw):
+    """The training loss of `model(inputs)` plus a sequence-level term over a candidate list, from
+    ONE encode -> (loss, terms):
+        loss = l_ptr + pairwise_loss_lam * l_pair + seq_lam * l_seq
+    l_ptr is the gold order's score / (N - 1) and l_pair the pairwise NLL, both as _forward
+    computes them (:1140-1172, stories of full length N); l_seq = order_loss(objective, **loss_kw)
+    over the candidates. The gold order is candidate 0; the others are `samples` ancestral
+    samples (sample_orders_batch, seed), the beam's n-best list or all N! orders (N <= 7), chosen
+    without a gradient; a repeat of an earlier candidate is taken out of the list. `terms` holds
+    "ptr", "pair" and "seq", detached. trainer.train_step takes
+    `lambda inp: (sequence_loss(args, model, inp, ...)[0],)` as its model."""
+    import itertools
+    if candidates not in ("sample", "nbest", "all"):
+        raise ValueError(f"candidates must be 'sample', 'nbest' or 'all', got {candidates!r}")
+    berson = _batch_inputs(model, inputs)
+    enc = model.encode(**berson)
+    gold = berson["ground_truth"]
+    B, N = gold.shape
+    dev = gold.device
+    with torch.no_grad():
+        if candidates == "sample":
+            others, _nll = sample_orders_batch(args, model, enc, samples, seed)
+        elif candidates == "nbest":
+            others, _nll, _count = beam_nbest_batch(args, model, enc)
+        else:
+            if N > EXACT_MAX_N:
+                raise ValueError(f"candidates='all' enumerates N! orders: N = {N} exceeds "
+                                 f"{EXACT_MAX_N}")
+            others = torch.tensor(list(itertools.permutations(range(N))), dtype=torch.int64,
+                                  device=dev)[None].expand(B, -1, -1)
+        orders = _candidate_set(torch.cat([gold[:, None], others], 1)).contiguous()
+    nll = score_orders_grad(args, model, enc, orders)
+    l_ptr = (nll[:, 0] / max(N - 1, 1)).sum() / B
+    cls_score = enc[6]
+    pairwise_labels, pairs_num = berson["pairwise_labels"], berson["pairs_num"]
+    npair = pairwise_labels.shape[1]
+    lc = torch.log_softmax(cls_score, -1)
+    pnll = -lc.gather(-1, pairwise_labels.reshape(-1, 1)).view(B, npair)
+    pmask = (torch.arange(npair, device=dev)[None] < pairs_num[:, None]).float()
+    l_pair = ((pnll * pmask).sum(-1) / (pairs_num.float() + 1e-20)).sum() / B
+    l_seq = order_loss(nll, orders, gold, objective, **loss_kw)
+    terms = {"ptr": l_ptr.detach(), "pair": l_pair.detach(), "seq": l_seq.detach()}
+    return l_ptr + model.pairwise_loss_lam * l_pair + seq_lam * l_seq, terms
+
+
 def exact_from_scores(nll):
     """nll [B][K] -> (index of the smallest score [B], that score [B], second-smallest minus
     smallest [B]; inf where K = 1). Ties go to the LOWEST candidate index, stated here instead of

@@ -945,6 +945,98 @@ class PointerFn(torch.autograd.Function):
         return dq, dkey, dokey, None, None, None, None, None, None, None
 
 
+ORDER_WEIGHTS = ("decoder.weight_ih_l0", "decoder.bias_ih_l0", "decoder.weight_hh_l0",
+                 "decoder.bias_hh_l0", "query_linear.weight", "query_linear.bias", "pw_k.weight",
+                 "tanh_linear.weight", "tanh_linear.bias")
+ORDER_WEIGHTS_T = ("decoder.weight_ih_l0", "decoder.weight_hh_l0", "query_linear.weight",
+                   "pw_k.weight")
+
+
+def order_grad_chunk(B, Nn, H, Kn, cap):
+    """-> (candidates per call, bytes): the largest count, halving from Kn, whose
+    mmseq_order_score_bwd workspace fits `cap` bytes (a single candidate is always tried);
+    bytes 0 = unsupported shape."""
+    kc = Kn
+    while kc > 1:
+        nbytes = N.order_score_bwd_workspace(B, Nn, H, kc)
+        if 0 < nbytes <= cap:
+            return kc, nbytes
+        kc = (kc + 1) // 2
+    return 1, N.order_score_bwd_workspace(B, Nn, H, 1)
+
+
+def _order_ws(store, nbytes, device):
+    """One workspace per store, grown on demand: it serves the forward and the backward."""
+    ws = getattr(store, "_order_grad_ws", None)
+    if ws is None or ws.numel() * 4 < nbytes or ws.device != device:
+        ws = store._order_grad_ws = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+    return ws
+
+
+class OrderScoreFn(torch.autograd.Function):
+    """nll [B][K] = mmseq_order_score of K candidate orders per story (orders int64 [K][N] or
+    [B][K][N] on the device), differentiable in doc, okey, hist, h0, c0 and the nine decoder
+    weights of `store` (mmseq_order_score_bwd; weight gradients accumulate into store.g(...) like
+    PointerFn's). K is split into chunks whose backward workspace stays within `cap` bytes; the
+    chunks' input gradients are added in chunk order. An unsupported shape raises
+    _native.Unsupported in the forward."""
+
+    @staticmethod
+    def forward(ctx, doc, okey, hist, h0, c0, anchor, store, orders, cap):
+        B, Nn, H = doc.shape
+        Kn = int(orders.shape[-2])
+        doc, okey, hist = doc.contiguous(), okey.contiguous(), hist.contiguous()
+        h0, c0, orders = h0.contiguous(), c0.contiguous(), orders.contiguous()
+        kc, nbytes = order_grad_chunk(B, Nn, H, Kn, cap)
+        if nbytes == 0 or N.order_score_workspace(B, Nn, H, kc) == 0:
+            raise N.Unsupported(f"OrderScoreFn: B={B} N={Nn} H={H} K={Kn} is outside "
+                                "mmseq_order_score's limits")
+        ws = _order_ws(store, max(nbytes, N.order_score_workspace(B, Nn, H, kc)), doc.device)
+        weights = [store.f32(n) for n in ORDER_WEIGHTS]
+        nll = torch.empty(B, Kn, dtype=torch.float32, device=doc.device)
+        for k0 in range(0, Kn, kc):
+            k = min(kc, Kn - k0)
+            whole = k == Kn
+            o_c = orders if whole else orders[..., k0:k0 + k, :].contiguous()
+            n_c = nll if whole else torch.empty(B, k, dtype=torch.float32, device=doc.device)
+            N._check_shape(N.order_score(doc, okey, hist, h0, c0, weights, o_c, n_c, None, ws),
+                           "mmseq_order_score")
+            if not whole:
+                nll[:, k0:k0 + k] = n_c
+        ctx.save_for_backward(doc, okey, hist, h0, c0, orders)
+        ctx.meta = (store, kc)
+        return nll
+
+    @staticmethod
+    def backward(ctx, dnll):
+        doc, okey, hist, h0, c0, orders = ctx.saved_tensors
+        store, kc = ctx.meta
+        B, Nn, H = doc.shape
+        Kn = int(orders.shape[-2])
+        if store.shadow_stale:  # the transposed copies the data-gradient GEMMs read
+            store.refresh_shadows()
+        weights = [store.f32(n) for n in ORDER_WEIGHTS]
+        weights_t = [store.wt(n) for n in ORDER_WEIGHTS_T]
+        dweights = [store.g(n) for n in ORDER_WEIGHTS]
+        ws = _order_ws(store, N.order_score_bwd_workspace(B, Nn, H, kc), doc.device)
+        dnll = dnll.contiguous().float()
+        total = None
+        for k0 in range(0, Kn, kc):
+            k = min(kc, Kn - k0)
+            whole = k == Kn
+            o_c = orders if whole else orders[..., k0:k0 + k, :].contiguous()
+            g_c = dnll if whole else dnll[:, k0:k0 + k].contiguous()
+            dins = [torch.empty_like(t) for t in (doc, okey, hist, h0, c0)]
+            N._check_shape(N.order_score_bwd(doc, okey, hist, h0, c0, weights, weights_t, o_c, g_c,
+                                             dins, dweights, ws), "mmseq_order_score_bwd")
+            if total is None:
+                total = dins
+            else:
+                for a, d in zip(total, dins):
+                    a.add_(d)
+        return (*total, None, None, None, None)
+
+
 # ================================================================================================
 # text+image pretraining: row selection and the masked-LM loss over the labelled rows
 # ================================================================================================
