@@ -152,13 +152,12 @@ class BertForOrdering(nn.Module):
     def forward(self, inputs):
         """BertForOrdering.forward (:937-941): inputs = {input_ids [B][L], labels [B][N],
         images [B][N][3][R][R] (optional), ...} -> (loss,)."""
-        berson = prepare_berson_inputs(inputs["input_ids"], inputs["labels"], self.n_steps,
-                                       device=self.device_)
-        images = inputs.get("images")
-        if images is not None:
-            images = images.to(self.device_, torch.float32, non_blocking=True).contiguous()
-        berson["images"] = images
-        return self._forward(**berson)
+        return self._forward(**_batch_inputs(self, inputs, non_blocking=True))
+
+    @property
+    def img_part(self):
+        """args.multimodal_img_part: the image-only model (no text, no joint stack)."""
+        return bool(getattr(self.args, "multimodal_img_part", False))
 
     def encode(self, input_ids, attention_mask=None, token_type_ids=None, pairs_list=None,
                passage_length=None, pairs_num=None, sep_positions=None, ground_truth=None,
@@ -175,17 +174,39 @@ class BertForOrdering(nn.Module):
         D.training = D.training and self.training
         self._drops = D
         ph = self.hidden_dropout_prob
-        joint, Lt = self.bert.encode_joint(input_ids.reshape(P, Lt),
-                                           attention_mask.reshape(P, Lt),
-                                           token_type_ids.reshape(P, Lt),
-                                           images if not self.bert.text_part else None,
-                                           pairs_list, drops=D, text_rows=True)
-        top = joint[:, :Lt].float()  # lang_feats (:1289), fp32 for the head
-        cls_pooled = top[:, 0]  # :1290
+        inner_img = bool(getattr(self.bert, "img_part", False))
+        if self.img_part != inner_img:
+            raise ValueError(f"args.multimodal_img_part = {self.img_part} but the inner model was "
+                             f"built with multimodal_img_part = {inner_img}: the "
+                             "head would pool rows of the wrong modality")
+        if self.img_part:
+            if images is None:
+                raise ValueError("an image-only model (multimodal_img_part) needs images")
+            # :1284-1290 with lxrt:1576-1582: lang_feats IS visn_feats [P][Tv][H]; kept in the
+            # compute dtype (the span pool and sentence_tran read bf16 rows, no fp32 copy)
+            rows, Lt = self.bert.encode_visual(images, pairs_list, drops=D)
+            top = rows
+            cls_pooled = rows[:, 0].float()  # the class-token row, not the pooler's output
+            # :1326-1328 shifts sep_positions in place by [Tv // 2 - 1, Tv - 2] -> [g^2 - 1, 2 g^2]
+            # from [0, 1]: the last patch of the first image is pooled with the second image.
+            # Built out of place here: the caller's tensor is left as it was.
+            if ("sep_shift", Lt) not in self._maps:
+                self._maps[("sep_shift", Lt)] = torch.tensor([Lt // 2 - 1, Lt - 2],
+                                                             device=self.device_)
+            sep_positions = sep_positions + self._maps[("sep_shift", Lt)]
+        else:
+            joint, Lt = self.bert.encode_joint(input_ids.reshape(P, Lt),
+                                               attention_mask.reshape(P, Lt),
+                                               token_type_ids.reshape(P, Lt),
+                                               images if not self.bert.text_part else None,
+                                               pairs_list, drops=D, text_rows=True)
+            rows = joint[:, :Lt]
+            top = rows.float()  # lang_feats (:1289), fp32 for the head
+            cls_pooled = top[:, 0]  # :1290
         # ---- HierarchicalAttention (:686-817) -------------------------------------------
         t = "two_level_encoder."
-        if joint.dtype == torch.bfloat16:  # the head's one large GEMM on the bf16 MFMA kernels
-            st = K.LinearLowpFn.apply(joint[:, :Lt], self._anchor, self.store,
+        if rows.dtype == torch.bfloat16:  # the head's one large GEMM on the bf16 MFMA kernels
+            st = K.LinearLowpFn.apply(rows, self._anchor, self.store,
                                       t + "sentence_tran.weight", t + "sentence_tran.bias", K.TANH)
         else:
             st = self._lin(top, t + "sentence_tran", act=K.TANH)
@@ -452,23 +473,27 @@ def beam_search_pointer_batch(args, model, input_ids, attention_mask=None, token
 
 def berson_pointer_network(args, model, tokenizer, inputs):
     """:1405-1408 — ordering indices for one story."""
-    berson = prepare_berson_inputs(inputs["input_ids"], inputs["labels"], model.n_steps,
-                                   device=model.device_)
+    return beam_search_pointer(args, model, **_batch_inputs(model, inputs))
+
+
+def _batch_inputs(model, inputs, non_blocking=False):
+    """The berson_inputs dict (+ images on the device) of a story batch. An image-only model
+    (args.multimodal_img_part) may get a batch without "input_ids" and "labels": the story count
+    and N come from the images, the labels default to 0 .. N-1."""
     images = inputs.get("images")
+    img_part = model.img_part
+    if img_part:
+        if images is None:
+            raise ValueError("an image-only model (multimodal_img_part) needs inputs['images']")
+        ids, labels = inputs.get("input_ids"), inputs.get("labels")
+        if labels is None:
+            labels = torch.arange(images.shape[1]).expand(images.shape[0], -1)
+    else:
+        ids, labels = inputs["input_ids"], inputs["labels"]
+    berson = prepare_berson_inputs(ids, labels, model.n_steps, device=model.device_,
+                                   img_part=img_part)
     if images is not None:
-        images = images.to(model.device_, torch.float32).contiguous()
-    berson["images"] = images
-    return beam_search_pointer(args, model, **berson)
-
-
-
-
-def _batch_inputs(model, inputs):
-    berson = prepare_berson_inputs(inputs["input_ids"], inputs["labels"], model.n_steps,
-                                   device=model.device_)
-    images = inputs.get("images")
-    if images is not None:
-        images = images.to(model.device_, torch.float32).contiguous()
+        images = images.to(model.device_, torch.float32, non_blocking=non_blocking).contiguous()
     berson["images"] = images
     return berson
 

@@ -262,6 +262,14 @@ def lxrt_from_pretrained(cls, pretrained_model_name_or_path, state_dict=None, ca
     elif has_bert and any(k.startswith("roberta.") for k in state_dict):
         state_dict = roberta_to_bert_keys(state_dict, set(model.state_dict().keys()))
     model.loading_info = load_into(model, state_dict, prefix)
+    if prefix:
+        # the checkpoint of a wrapper (LXRTPretraining -> LXRTModel): the wrapper's own heads lie
+        # outside the prefix; they are not loaded, and reported with the unexpected keys
+        outside = [k for k in state_dict if not k.startswith(prefix)]
+        if outside:
+            logger.info("Weights from pretrained model outside '%s', not used in %s: %s", prefix,
+                        type(model).__name__, outside)
+            model.loading_info["unexpected_keys"] += outside
     return model
 
 

@@ -703,6 +703,39 @@ class JointInputFn(torch.autograd.Function):
 
 
 # ================================================================================================
+# Image-only input (multimodal_img_part): JointInputFn's visual half on its own, visn_fc (Linear +
+# LN + dropout, lxrt:569-602) over the ViT rows -> [P*Tv][H]; no embedding is computed
+# ================================================================================================
+class VisnInputFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, vout, anchor, L, eps, drop=None):
+        st = L.store
+        vpre = _linear(vout, st.w(L.v_w), bias=st.f32(L.v_b))
+        R, H = vpre.shape
+        out = torch.empty_like(vpre)
+        mv = torch.empty(R, device=vout.device)
+        rv = torch.empty_like(mv)
+        N.layernorm_fwd(R, H, vpre, _rows(H), st.f32(L.vln_w), st.f32(L.vln_b), eps, out, _rows(H),
+                        mv, rv, drop=drop)
+        ctx.save_for_backward(vout, vpre, mv, rv)
+        ctx.meta = (L, drop)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        L, drop = ctx.meta
+        st = L.store
+        vout, vpre, mv, rv = ctx.saved_tensors
+        R, H = vpre.shape
+        dvpre = torch.empty_like(vpre)
+        N.layernorm_bwd(R, H, dout.contiguous(), _rows(H), vpre, _rows(H), mv, rv, st.f32(L.vln_w),
+                        dvpre, _rows(H), None, _rows(H), st.g(L.vln_w), st.g(L.vln_b), drop_dy=drop)
+        _wgrad(dvpre, vout, st.g(L.v_w), st.g(L.v_b))
+        st.grad_ready(L.span)
+        return _dgrad(dvpre, st.wt(L.v_w)), None, None, None, None
+
+
+# ================================================================================================
 # generic pieces used by the (small, fp32) BERSON head
 # ================================================================================================
 class LinearFn(torch.autograd.Function):

@@ -163,7 +163,11 @@ class LXRTModel(nn.Module):
         self.rn50 = None
         if not multimodal_text_part and self.vision.get("type") == "rn50":
             if multimodal_img_part:
-                raise NotImplementedError("image-only pretraining runs the ViT backbones")
+                raise NotImplementedError(
+                    "image-only pretraining and ordering run the ViT backbones: with RN50 the "
+                    "reference yields one sequence per image, so its ordering head's reshape test "
+                    "(modeling_bert.py:1320) never fires for N > 2 and sep_positions no longer "
+                    "matches top_vec")
             from .resnet import RN50Backbone, rn50_buffer_names
             bufs = {}
             for name, c in rn50_buffer_names(VIT, self.vision["layers"],
@@ -265,6 +269,25 @@ class LXRTModel(nn.Module):
             h = K.VitBlockFn.apply(h, self._anchor, L, P, Tv, heads, 1e-5, save)
         return K.VitProjFn.apply(h, self._anchor, self.proj_refs), Tv
 
+    def encode_visual(self, images, pairs_list, drops=None):
+        """The image-only encoder (multimodal_img_part, lxrt:1066-1069, 1576-1582): the pair-sequence
+        ViT, its projection, then visn_fc + LayerNorm with the visn_fc dropout site; there is no
+        BertLayer stack and no text embedding. images [B][N][3][R][R] f32, pairs_list
+        [B][npair][2] -> (visn_feats [P][Tv][H] in the compute dtype, Tv = 1 + 2 g^2)."""
+        if self.text_part or self.rn50 is not None:
+            raise NotImplementedError("encode_visual runs the ViT backbones of a model with a "
+                                      "visual part")
+        if images is None:
+            raise ValueError("encode_visual needs images")
+        st = self.store
+        D = drops or self.new_dropouts()
+        if st.shadow_stale:
+            st.refresh_shadows()
+        vout, Tv = self.visual_forward(images, pairs_list)
+        x = K.VisnInputFn.apply(vout, self._anchor, self.input_refs, 1e-12,
+                                D.site(self.config.hidden_dropout_prob, "visn_fc"))
+        return x.view(-1, Tv, x.shape[-1]), Tv
+
     def encode_joint(self, input_ids, attention_mask, token_type_ids=None, images=None,
                      pairs_list=None, drops=None, text_rows=False, visual_row_op=None):
         """Run embeddings (+ ViT + visn_fc) and the joint BERT stack. visual_row_op (vout
@@ -317,6 +340,13 @@ class LXRTModel(nn.Module):
             imgs = visual_feats.reshape(-1, 2, 3, R, R).float().contiguous()
             pl = torch.tensor([[[0, 1]]], device=imgs.device).expand(imgs.shape[0], 1, 2).contiguous()
             visual_feats, pairs_list = imgs, pl
+        if self.img_part:
+            # lxrt:1526-1530, 1576-1582: the language side shrinks to a CLS embedding that nothing
+            # reads (not computed here), the visual rows take lang_feats' slot
+            visn, _Tv = self.encode_visual(visual_feats, pairs_list)
+            pooled = K.LinearFn.apply(visn[:, 0], self._anchor, self.store, "pooler.dense.weight",
+                                      "pooler.dense.bias", 0)
+            return (visn, None), pooled
         joint, Lt = self.encode_joint(input_ids, attention_mask, token_type_ids, visual_feats,
                                       pairs_list)
         lang = joint[:, :Lt]

@@ -31,29 +31,35 @@ PRESETS = {
                                max_position_embeddings=514),
                     vision="ViT-L/14", N=9, per_seq=128, ff=3072),
 }
+# image-only ordering (--multimodal_img_part): the same vision tower and head, no joint stack; the
+# consumer of the image-only pretraining stage's checkpoint (pretraining.py, config 2). ViT only.
+PRESETS["config3_imgonly"] = dict(PRESETS["config3"], img_only=True)
+PRESETS["config5_imgonly"] = dict(PRESETS["config5"], img_only=True)
 
 
-def berson_args(N, per_seq, ff=3072, heads=8, inter_layers=2, beam=16, lam=0.6, text_only=False):
+def berson_args(N, per_seq, ff=3072, heads=8, inter_layers=2, beam=16, lam=0.6, text_only=False,
+                img_only=False):
     return argparse.Namespace(ff_size=ff, heads=heads, para_dropout=0.1, inter_layers=inter_layers,
                               beam_size=beam, pairwise_loss_lam=lam, multimodal_loss=False,
                               multimodal=True, multimodal_text_part=text_only,
                               multimodal_model_type="clip", per_seq_max_length=per_seq,
-                              max_story_length=N, multimodal_img_part=False)
+                              max_story_length=N, multimodal_img_part=img_only)
 
 
 def build(joint, vision, N, per_seq, ff=3072, heads=8, inter_layers=2, text_only=False,
-          device="cuda", dtype=torch.bfloat16, seed=0):
-    """Returns BertForOrdering with .bert = LXRTModel (train.py:2024-2028)."""
+          device="cuda", dtype=torch.bfloat16, seed=0, img_only=False):
+    """Returns BertForOrdering with .bert = LXRTModel (train.py:2024-2028). img_only: the
+    image-only model (multimodal_img_part on the inner model and on args; ViT backbones only)."""
     cfg = LXRTConfig(**joint)
     vis = None
     if not text_only:
         vis = dict(vision) if isinstance(vision, dict) else dict(CLIP_VISION[vision])
-    inner = LXRTModel(cfg, multimodal_text_part=text_only, cls_id=0, sep_id=2, max_story_length=N,
-                      device=device, compute_dtype=dtype, vision=vis, seed=seed,
+    inner = LXRTModel(cfg, multimodal_text_part=text_only, multimodal_img_part=img_only,
+                      cls_id=0, sep_id=2, max_story_length=N, device=device, compute_dtype=dtype, vision=vis, seed=seed,
                       clip_model_name=vision if isinstance(vision, str) else
                       ("RN50" if vis and vis.get("type") == "rn50" else "ViT-B/16"))
     args = berson_args(N, per_seq, ff=ff, heads=heads, inter_layers=inter_layers,
-                       text_only=text_only)
+                       text_only=text_only, img_only=img_only)
     model = BertForOrdering(BersonConfig(hidden_size=cfg.hidden_size), args, device=device,
                             seed=seed + 1)
     model.bert = inner
@@ -63,7 +69,8 @@ def build(joint, vision, N, per_seq, ff=3072, heads=8, inter_layers=2, text_only
 def build_preset(name, device="cuda", dtype=torch.bfloat16, seed=0):
     p = PRESETS[name]
     return build(p["joint"], p["vision"], p["N"], p["per_seq"], ff=p["ff"],
-                 text_only=p["vision"] is None, device=device, dtype=dtype, seed=seed)
+                 text_only=p["vision"] is None, device=device, dtype=dtype, seed=seed,
+                 img_only=p.get("img_only", False))
 
 
 def build_from_golden(cfg, device="cuda", dtype=torch.float32):
@@ -80,7 +87,8 @@ def build_from_golden(cfg, device="cuda", dtype=torch.float32):
                       embed=V["embed"])
     H = cfg["head"]
     return build(joint, vision, cfg["N"], cfg["per_seq"], ff=H["ff"], heads=H["heads"],
-                 inter_layers=H["layers"], text_only=cfg["text_only"], device=device, dtype=dtype)
+                 inter_layers=H["layers"], text_only=cfg["text_only"], device=device, dtype=dtype,
+                 img_only=cfg.get("img_only", False))
 
 
 def build_pretrain_mm_from_golden(cfg, objectives, device="cuda", dtype=torch.float32):

@@ -34,13 +34,46 @@ def _split_steps(row, n_steps, cls_id, sep_id):
 
 
 def prepare_berson_inputs(input_ids, labels, n_steps, cls_id=CLS_ID, sep_id=SEP_ID, pad_id=PAD_ID,
-                          device=None):
+                          device=None, img_part=False):
     """Returns the reference's berson_inputs dict (:47-60) as int64 tensors (on `device`): by the
-    device kernels when `device` is a GPU, else on the host."""
+    device kernels when `device` is a GPU, else on the host. img_part (args.multimodal_img_part,
+    :198-204): `sep_positions` is [0, 1] for every pair, everything else is unchanged; input_ids
+    may then be None (an image-only batch carries no text): the pair text tensors are the minimal
+    placeholders of prepare_imgonly_inputs."""
+    if input_ids is None:
+        if not img_part:
+            raise ValueError("input_ids may be omitted for an image-only batch (img_part) only")
+        return prepare_imgonly_inputs(labels, n_steps, cls_id, sep_id, device)
     if device is not None and torch.device(device).type == "cuda":
         return prepare_berson_inputs_device(input_ids, labels, n_steps, cls_id, sep_id, pad_id,
-                                            device)
-    return prepare_berson_inputs_host(input_ids, labels, n_steps, cls_id, sep_id, pad_id, device)
+                                            device, img_part)
+    return prepare_berson_inputs_host(input_ids, labels, n_steps, cls_id, sep_id, pad_id, device,
+                                      img_part)
+
+
+def prepare_imgonly_inputs(labels, n_steps, cls_id=CLS_ID, sep_id=SEP_ID, device=None):
+    """The berson_inputs dict of an image-only batch without text: labels [B][N] alone fix the
+    story count, the gold order and the pairwise labels; every pair's text is the placeholder
+    `<s> </s>` (never embedded in this mode) and `sep_positions` is [0, 1]."""
+    lab = torch.as_tensor(labels).to(device or "cpu", torch.int64).contiguous()
+    B, N = lab.shape
+    if N != n_steps:
+        raise ValueError(f"labels shape {tuple(lab.shape)} != ({B}, {n_steps})")
+    dev = lab.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    pa = _pairs_on(dev, N)
+    npair = pa.shape[0]
+    rank = lab.argsort(1)  # rank[b][s] = position of sentence s in the gold order (:162-174)
+    plab = (rank[:, pa[:, 0]] < rank[:, pa[:, 1]]).to(torch.int64)
+    ids = torch.tensor([cls_id, sep_id], **i64).expand(B, npair, 2).contiguous()
+    return {
+        "input_ids": ids, "attention_mask": torch.ones_like(ids),
+        "token_type_ids": torch.zeros_like(ids),
+        "pairs_list": pa[None].expand(B, npair, 2).contiguous(),
+        "passage_length": torch.full((B,), N, **i64), "pairs_num": torch.full((B,), npair, **i64),
+        "sep_positions": torch.tensor([0, 1], **i64).expand(B, npair, 2).contiguous(),
+        "ground_truth": lab, "mask_cls": torch.ones(B, N, **i64), "pairwise_labels": plab,
+    }
 
 
 _PAIRS_CACHE = {}
@@ -55,7 +88,7 @@ def _pairs_on(device, n_steps):
 
 
 def prepare_berson_inputs_device(input_ids, labels, n_steps, cls_id=CLS_ID, sep_id=SEP_ID,
-                                 pad_id=PAD_ID, device="cuda"):
+                                 pad_id=PAD_ID, device="cuda", img_part=False):
     """mmseq_pair_scan + mmseq_pair_expand; host ids are copied to the device first."""
     from . import _native as NT
     dev = torch.device(device)
@@ -77,6 +110,8 @@ def prepare_berson_inputs_device(input_ids, labels, n_steps, cls_id=CLS_ID, sep_
                          "<s> ... </s> steps (process_inputs_for_berson.py:104,136)")
     out_ids, mask, tt = (torch.empty(B * npair, Lp, **i64) for _ in range(3))
     NT.pair_expand(ids, starts, lens, N, Lp, pad_id, cls_id != 0, out_ids, mask, tt)
+    if img_part:  # :198-204: the text is parsed for the step count, its </s> positions are not used
+        sep = torch.tensor([0, 1], **i64).expand(B, npair, 2).contiguous()
     return {
         "input_ids": out_ids.view(B, npair, Lp), "attention_mask": mask.view(B, npair, Lp),
         "token_type_ids": tt.view(B, npair, Lp),
@@ -88,7 +123,7 @@ def prepare_berson_inputs_device(input_ids, labels, n_steps, cls_id=CLS_ID, sep_
 
 
 def prepare_berson_inputs_host(input_ids, labels, n_steps, cls_id=CLS_ID, sep_id=SEP_ID,
-                               pad_id=PAD_ID, device=None):
+                               pad_id=PAD_ID, device=None, img_part=False):
     """Host (numpy) restatement of the same expansion."""
     ids = input_ids.detach().cpu().numpy() if torch.is_tensor(input_ids) else np.asarray(input_ids)
     lab = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
@@ -120,6 +155,8 @@ def prepare_berson_inputs_host(input_ids, labels, n_steps, cls_id=CLS_ID, sep_id
     else:
         tt = np.where(in2, 1, 0)
     sep = np.stack([l1 - 1, plen - 1], -1)
+    if img_part:  # :198-204
+        sep = np.broadcast_to(np.array([0, 1], np.int64), sep.shape)
     # pairwise label = 1 iff sentence a comes before sentence c in the ground-truth order (:162-174)
     rank = np.argsort(lab, axis=1)  # rank[b][s] = position of sentence s in the gold order
     ra = np.take_along_axis(rank, np.broadcast_to(pa[None, :, 0], (B, npair)), 1)
