@@ -659,6 +659,14 @@ def lstm_cell_bwd(act, c, c_out, dh, dc_next, dgates, dc_prev):
 EUNSUPPORTED = -2
 
 
+def _status(st, name):
+    """The tail of every wrapper below: MMSEQ_EUNSUPPORTED comes back as the status (the caller
+    decides what to do instead), every other failure raises."""
+    if st != EUNSUPPORTED:
+        _check(st, name)
+    return st
+
+
 def beam_workspace(B, N, H, W):
     """Bytes of workspace mmseq_beam_search needs; 0 where the shape is unsupported."""
     return int(lib().mmseq_beam_workspace(B, N, H, W))
@@ -706,9 +714,7 @@ def beam_search(doc, okey, hist, h0, c0, weights, W, order, score, workspace):
                         ((order, torch.int64, (B, N)), (score, torch.float32, (B,))))
     st = lib().mmseq_beam_search(B, N, H, int(W), *ptrs, _p(order), _p(score), _p(workspace),
                                  _ws_bytes(workspace), _stream())
-    if st != EUNSUPPORTED:
-        _check(st, "mmseq_beam_search")
-    return st
+    return _status(st, "mmseq_beam_search")
 
 
 def beam_search_nbest(doc, okey, hist, h0, c0, weights, W, orders, scores, count, workspace):
@@ -722,9 +728,7 @@ def beam_search_nbest(doc, okey, hist, h0, c0, weights, W, orders, scores, count
                          (count, torch.int32, (B,))))
     st = lib().mmseq_beam_search_nbest(B, N, H, W, *ptrs, _p(orders), _p(scores), _p(count),
                                        _p(workspace), _ws_bytes(workspace), _stream())
-    if st != EUNSUPPORTED:
-        _check(st, "mmseq_beam_search_nbest")
-    return st
+    return _status(st, "mmseq_beam_search_nbest")
 
 
 def order_score_workspace(B, N, H, K):
@@ -749,9 +753,7 @@ def order_score(doc, okey, hist, h0, c0, weights, orders, nll, step_nll, workspa
     st = lib().mmseq_order_score(B, N, H, K, *ptrs, _p(orders), 0 if orders.dim() == 2 else K * N,
                                  _p(nll), _p(step_nll) if step_nll is not None else None,
                                  _p(workspace), _ws_bytes(workspace), _stream())
-    if st != EUNSUPPORTED:
-        _check(st, "mmseq_order_score")
-    return st
+    return _status(st, "mmseq_order_score")
 
 
 def order_score_bwd_workspace(B, N, H, K):
@@ -792,9 +794,7 @@ def order_score_bwd(doc, okey, hist, h0, c0, weights, weights_t, orders, dnll, d
                                      0 if orders.dim() == 2 else K * N, _p(dnll),
                                      *[_p(t) for t in dins], *[_p(t) for t in dweights],
                                      _p(workspace), _ws_bytes(workspace), _stream())
-    if st != EUNSUPPORTED:
-        _check(st, "mmseq_order_score_bwd")
-    return st
+    return _status(st, "mmseq_order_score_bwd")
 
 
 def order_sample_workspace(B, N, H, S):
@@ -822,9 +822,7 @@ def order_sample(doc, okey, hist, h0, c0, weights, seed, stream_id, story0, samp
                                   int(stream_id) & 0xFFFFFFFF, int(story0), int(sample0),
                                   _p(orders), _p(nll), _p(u), _p(step_nlp), _p(workspace),
                                   _ws_bytes(workspace), _stream())
-    if st != EUNSUPPORTED:
-        _check(st, "mmseq_order_sample")
-    return st
+    return _status(st, "mmseq_order_sample")
 
 
 def order_tree_workspace(B, N, H, rows):
@@ -847,9 +845,7 @@ def order_tree(doc, okey, hist, h0, c0, weights, rows, nll, orders, workspace):
     st = lib().mmseq_order_tree(B, N, H, *ptrs, int(rows), _p(nll),
                                 _p(orders) if orders is not None else None, _p(workspace),
                                 _ws_bytes(workspace), _stream())
-    if st != EUNSUPPORTED:
-        _check(st, "mmseq_order_tree")
-    return st
+    return _status(st, "mmseq_order_tree")
 
 
 POSTERIOR_MODES = {"weights": 0, "uniform": 1}
@@ -883,9 +879,7 @@ def order_posterior(orders, nll, mode, out):
                                      0 if orders.dim() == 2 else K * N, _p(nll),
                                      *(_p(out[name]) for name, _, _ in POSTERIOR_OUTPUTS),
                                      _stream())
-    if st != EUNSUPPORTED:
-        _check(st, "mmseq_order_posterior")
-    return st
+    return _status(st, "mmseq_order_posterior")
 
 
 # name -> (dtype, trailing shape in units of N) of mmseq_pairwise_order's outputs, in ABI order
@@ -918,9 +912,7 @@ def pairwise_order(w, out, workspace):
                              f"{tuple(t.shape)} {t.dtype}")
     st = lib().mmseq_pairwise_order(B, N, _p(w), *(_p(out[name]) for name, _, _ in PAIRWISE_OUTPUTS),
                                     _p(workspace), _ws_bytes(workspace), _stream())
-    if st != EUNSUPPORTED:
-        _check(st, "mmseq_pairwise_order")
-    return st
+    return _status(st, "mmseq_pairwise_order")
 
 
 def pairwise_score(w, orders, pnll):
@@ -940,9 +932,7 @@ def pairwise_score(w, orders, pnll):
                              f"{tuple(t.shape)} {t.dtype}")
     st = lib().mmseq_pairwise_score(B, N, K, _p(w), _p(orders),
                                     0 if orders.dim() == 2 else K * N, _p(pnll), _stream())
-    if st != EUNSUPPORTED:
-        _check(st, "mmseq_pairwise_score")
-    return st
+    return _status(st, "mmseq_pairwise_score")
 
 
 class Unsupported(NativeError):

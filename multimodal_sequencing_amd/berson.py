@@ -421,9 +421,29 @@ def _beam_decode_story(args, model, enc, b):
     return best + sorted(set(range(T)) - set(best))[:1], best_score
 
 
-_BEAM_WEIGHTS = ("decoder.weight_ih_l0", "decoder.bias_ih_l0", "decoder.weight_hh_l0",
-                 "decoder.bias_hh_l0", "query_linear.weight", "query_linear.bias", "pw_k.weight",
-                 "tanh_linear.weight", "tanh_linear.bias")
+def _decoder_inputs(model, enc):
+    """An encode() tuple -> (B, N, H, ins), `ins` the six inputs every decoder wrapper of _native
+    takes first: doc, okey, hist = (cls_mat, softmax(cs_mat)), h0, c0 (contiguous) and the nine
+    decoder weights. For the no-grad entries; OrderScoreFn takes the tensors with their graph."""
+    (sent, _p, dec_init, okeys, _cls, cls_mat, _cs, cs_mat, _h1, _h2) = enc
+    B, N, H = sent.shape
+    hist = torch.cat([cls_mat, torch.softmax(cs_mat, -1)], -1).contiguous()
+    return B, N, H, (sent.contiguous(), okeys.contiguous(), hist, dec_init[0][0].contiguous(),
+                     dec_init[1][0].contiguous(), [model.store.f32(n) for n in K.ORDER_WEIGHTS])
+
+
+def _fit_chunk(size_fn, n, low=1, cap=None):
+    """-> (count, bytes): the largest count, halving from n down to `low`, whose workspace of
+    size_fn(count) bytes fits `cap` (default: SCORE_WS_CAP, read at call time); `low` is taken
+    whatever it needs (a single candidate is always tried). bytes 0 = unsupported shape."""
+    if cap is None:
+        cap = SCORE_WS_CAP
+    while n > low:
+        nbytes = size_fn(n)
+        if 0 < nbytes <= cap:
+            return n, nbytes
+        n = max(low, (n + 1) // 2)
+    return low, size_fn(low)
 
 
 @torch.no_grad()
@@ -432,23 +452,16 @@ def beam_decode_batch(args, model, enc):
     the device, nothing synchronises until the caller reads the result) -> (order int64 [B][N],
     best score f32 [B]) on the device. Where the ABI reports the shape unsupported, the stories
     go through the per-story decoder one by one."""
-    (sent, _p, dec_init, okeys, _cls, cls_mat, _cs, cs_mat, _h1, _h2) = enc
-    B, N, H = sent.shape
+    B, N, H = enc[0].shape
     W = int(getattr(args, "beam_size", 16))
-    dev = sent.device
+    dev = enc[0].device
     order = torch.empty(B, N, dtype=torch.int64, device=dev)
     score = torch.empty(B, dtype=torch.float32, device=dev)
     nbytes = N_.beam_workspace(B, N, H, W)
     st = N_.EUNSUPPORTED
     if nbytes > 0:
-        cache = model.__dict__.setdefault("_beam_ws", {})
-        ws = cache.get((B, N, H, W))
-        if ws is None:
-            ws = cache[(B, N, H, W)] = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-        hist = torch.cat([cls_mat, torch.softmax(cs_mat, -1)], -1).contiguous()
-        st = N_.beam_search(sent.contiguous(), okeys.contiguous(), hist,
-                            dec_init[0][0].contiguous(), dec_init[1][0].contiguous(),
-                            [model.store.f32(n) for n in _BEAM_WEIGHTS], W, order, score, ws)
+        ws = K._cached_ws(model, "_beam_ws", (B, N, H, W), nbytes, dev)
+        st = N_.beam_search(*_decoder_inputs(model, enc)[3], W, order, score, ws)
     if st == N_.EUNSUPPORTED:
         res = [_beam_decode_story(args, model, enc, b) for b in range(B)]
         order = torch.tensor([r[0] for r in res], dtype=torch.int64, device=dev)
@@ -636,16 +649,22 @@ def score_orders_host(args, model, enc, orders, return_steps=False, chunk=128):
     return (nll, steps) if return_steps else nll
 
 
+def _device_orders(orders, B, N, dev):
+    """Candidate orders for a device entry: a device tensor is checked for shape only (no
+    synchronisation), anything else is validated on the host (check_orders) and copied."""
+    if torch.is_tensor(orders) and orders.is_cuda:
+        o = orders
+        if o.dtype != torch.int64 or o.dim() not in (2, 3) or o.shape[-1] != N or \
+                o.shape[-2] < 1 or (o.dim() == 3 and o.shape[0] != B):
+            raise ValueError(f"orders must be int64 [K][{N}] or [{B}][K][{N}] with K >= 1, got "
+                             f"{o.dtype} {tuple(o.shape)}")
+        return o
+    return check_orders(orders, B, N).to(dev)
+
+
 def _score_chunk(B, N, H, Kn):
-    """-> (candidates per call, workspace bytes): the largest count, halving from Kn, whose
-    workspace fits SCORE_WS_CAP (a single candidate is always tried); bytes 0 = unsupported."""
-    kc = Kn
-    while kc > 1:
-        nbytes = N_.order_score_workspace(B, N, H, kc)
-        if 0 < nbytes <= SCORE_WS_CAP:
-            return kc, nbytes
-        kc = (kc + 1) // 2
-    return 1, N_.order_score_workspace(B, N, H, 1)
+    """-> (candidates per call, workspace bytes) of mmseq_order_score under SCORE_WS_CAP."""
+    return _fit_chunk(lambda k: N_.order_score_workspace(B, N, H, k), Kn)
 
 
 @torch.no_grad()
@@ -663,34 +682,19 @@ def score_orders_batch(args, model, enc, orders, return_steps=False):
     per call (B = 32, H = 768, all 120 orders of N = 5 need 90 MiB: one call; the 5040 orders of
     N = 7 at H = 1024 go in chunks of 158). Where the ABI reports the shape
     unsupported (N > 16) the candidates go through score_orders_host."""
-    (sent, _p, dec_init, okeys, _cls, cls_mat, _cs, cs_mat, _h1, _h2) = enc
-    B, N, H = sent.shape
-    dev = sent.device
-    if torch.is_tensor(orders) and orders.is_cuda:
-        o = orders
-        if o.dtype != torch.int64 or o.dim() not in (2, 3) or o.shape[-1] != N or \
-                o.shape[-2] < 1 or (o.dim() == 3 and o.shape[0] != B):
-            raise ValueError(f"orders must be int64 [K][{N}] or [{B}][K][{N}] with K >= 1, got "
-                             f"{o.dtype} {tuple(o.shape)}")
-    else:
-        o = check_orders(orders, B, N).to(dev)
+    B, N, H = enc[0].shape
+    dev = enc[0].device
+    o = _device_orders(orders, B, N, dev)
     Kn = int(o.shape[-2])
     kc, nbytes = _score_chunk(B, N, H, Kn)
     if nbytes == 0:
         return score_orders_host(args, model, enc, o, return_steps)
     nll = torch.empty(B, Kn, dtype=torch.float32, device=dev)
     steps = torch.empty(B, Kn, N - 1, dtype=torch.float32, device=dev) if return_steps else None
-    hist = torch.cat([cls_mat, torch.softmax(cs_mat, -1)], -1).contiguous()
-    ins = (sent.contiguous(), okeys.contiguous(), hist, dec_init[0][0].contiguous(),
-           dec_init[1][0].contiguous(), [model.store.f32(n) for n in _BEAM_WEIGHTS])
-    cache = model.__dict__.setdefault("_score_ws", {})
-    for k0 in range(0, Kn, kc):
-        k = min(kc, Kn - k0)
+    ins = _decoder_inputs(model, enc)[3]
+    for k0, k, whole in K._chunks(Kn, kc):
         nb = nbytes if k == kc else N_.order_score_workspace(B, N, H, k)
-        ws = cache.get((B, N, H, k))
-        if ws is None:
-            ws = cache[(B, N, H, k)] = torch.empty(nb // 4, dtype=torch.float32, device=dev)
-        whole = k == Kn
+        ws = K._cached_ws(model, "_score_ws", (B, N, H, k), nb, dev)
         o_c = o if whole else o[..., k0:k0 + k, :].contiguous()
         nll_c = nll if whole else torch.empty(B, k, dtype=torch.float32, device=dev)
         st_c = None
@@ -715,19 +719,6 @@ def berson_score_orders(args, model, tokenizer, inputs, orders, return_steps=Fal
 
 # ------------------------------------------------------------------------------------------------
 # Gradients of candidate-order scores and sequence-level losses.
-def _device_orders(orders, B, N, dev):
-    """score_orders_batch's handling of `orders`: a device tensor is checked for shape only (no
-    synchronisation), anything else is validated on the host and copied."""
-    if torch.is_tensor(orders) and orders.is_cuda:
-        o = orders
-        if o.dtype != torch.int64 or o.dim() not in (2, 3) or o.shape[-1] != N or \
-                o.shape[-2] < 1 or (o.dim() == 3 and o.shape[0] != B):
-            raise ValueError(f"orders must be int64 [K][{N}] or [{B}][K][{N}] with K >= 1, got "
-                             f"{o.dtype} {tuple(o.shape)}")
-        return o
-    return check_orders(orders, B, N).to(dev)
-
-
 def score_orders_grad(args, model, enc, orders):
     """score_orders_batch with a graph: nll f32 [B][K] of K candidate orders per story, attached
     to the graph of the encode() tuple `enc` (K.OrderScoreFn: mmseq_order_score forward, the same
@@ -923,15 +914,9 @@ def _tree_rows(B, N, H):
     """-> (rows, workspace bytes) for mmseq_order_tree: the chunk cap, halving from the widest
     level's B * N! / 2 rows (unchunked) down to the minimum B * N, whose workspace fits
     SCORE_WS_CAP (the minimum is taken whatever it needs); bytes 0 = unsupported."""
-    import math
     low = max(B * N, 1)
-    rows = max(low, B * math.factorial(N) // 2)
-    while rows > low:
-        nbytes = N_.order_tree_workspace(B, N, H, rows)
-        if 0 < nbytes <= SCORE_WS_CAP:
-            return rows, nbytes
-        rows = max(low, (rows + 1) // 2)
-    return low, N_.order_tree_workspace(B, N, H, low)
+    return _fit_chunk(lambda rows: N_.order_tree_workspace(B, N, H, rows),
+                      max(low, B * math.factorial(N) // 2), low)
 
 
 @torch.no_grad()
@@ -944,29 +929,21 @@ def enumerate_orders_batch(args, model, enc, return_orders=False):
     ValueError above. The tree is walked in chunks of `rows` slot rows, the largest count whose
     workspace stays within SCORE_WS_CAP; the workspace is cached on the model like the beam's.
     A shape outside the ABI's limits raises _native.Unsupported."""
-    import math
-    (sent, _p, dec_init, okeys, _cls, cls_mat, _cs, cs_mat, _h1, _h2) = enc
-    B, N, H = sent.shape
+    B, N, H = enc[0].shape
     if N > TREE_MAX_N:
         raise ValueError(f"enumerate_orders_batch walks all N! orders: N = {N} exceeds "
                          f"{TREE_MAX_N}")
-    dev = sent.device
+    dev = enc[0].device
     rows, nbytes = _tree_rows(B, N, H)
     if nbytes == 0:
         raise N_.Unsupported(f"enumerate_orders_batch: B={B} N={N} H={H} is outside "
                              "mmseq_order_tree's limits")
-    K = math.factorial(N)
-    nll = torch.empty(B, K, dtype=torch.float32, device=dev)
-    orders = torch.empty(K, N, dtype=torch.int64, device=dev) if return_orders else None
-    cache = model.__dict__.setdefault("_tree_ws", {})
-    ws = cache.get((B, N, H, rows))
-    if ws is None:
-        ws = cache[(B, N, H, rows)] = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-    hist = torch.cat([cls_mat, torch.softmax(cs_mat, -1)], -1).contiguous()
-    N_._check_shape(N_.order_tree(sent.contiguous(), okeys.contiguous(), hist,
-                                  dec_init[0][0].contiguous(), dec_init[1][0].contiguous(),
-                                  [model.store.f32(n) for n in _BEAM_WEIGHTS], rows, nll, orders,
-                                  ws), "mmseq_order_tree")
+    Kn = math.factorial(N)
+    nll = torch.empty(B, Kn, dtype=torch.float32, device=dev)
+    orders = torch.empty(Kn, N, dtype=torch.int64, device=dev) if return_orders else None
+    ws = K._cached_ws(model, "_tree_ws", (B, N, H, rows), nbytes, dev)
+    N_._check_shape(N_.order_tree(*_decoder_inputs(model, enc)[3], rows, nll, orders, ws),
+                    "mmseq_order_tree")
     return (nll, orders) if return_orders else nll
 
 
@@ -1002,10 +979,9 @@ def beam_nbest_batch(args, model, enc):
     encode() tuple -> (orders int64 [B][W][N], scores f32 [B][W], count int32 [B]) on the device,
     ascending by score; entry 0 is beam_decode_batch's result. Rows count[b] .. W-1 hold -1 and
     +inf. W = args.beam_size. An unsupported shape raises (_native.Unsupported)."""
-    (sent, _p, dec_init, okeys, _cls, cls_mat, _cs, cs_mat, _h1, _h2) = enc
-    B, N, H = sent.shape
+    B, N, H = enc[0].shape
     W = int(getattr(args, "beam_size", 16))
-    dev = sent.device
+    dev = enc[0].device
     orders = torch.full((B, W, N), -1, dtype=torch.int64, device=dev)
     scores = torch.full((B, W), float("inf"), dtype=torch.float32, device=dev)
     count = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -1013,15 +989,9 @@ def beam_nbest_batch(args, model, enc):
     if nbytes == 0:
         raise N_.Unsupported(f"beam_nbest_batch: B={B} N={N} H={H} W={W} is outside "
                              "mmseq_beam_search's limits")
-    cache = model.__dict__.setdefault("_beam_ws", {})
-    ws = cache.get((B, N, H, W))
-    if ws is None:
-        ws = cache[(B, N, H, W)] = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-    hist = torch.cat([cls_mat, torch.softmax(cs_mat, -1)], -1).contiguous()
-    N_._check_shape(N_.beam_search_nbest(sent.contiguous(), okeys.contiguous(), hist,
-                                         dec_init[0][0].contiguous(), dec_init[1][0].contiguous(),
-                                         [model.store.f32(n) for n in _BEAM_WEIGHTS], W, orders,
-                                         scores, count, ws), "mmseq_beam_search_nbest")
+    ws = K._cached_ws(model, "_beam_ws", (B, N, H, W), nbytes, dev)
+    N_._check_shape(N_.beam_search_nbest(*_decoder_inputs(model, enc)[3], W, orders, scores, count,
+                                         ws), "mmseq_beam_search_nbest")
     return orders, scores, count
 
 
@@ -1067,17 +1037,6 @@ def order_posterior(orders, nll, mode="weights"):
     return out
 
 
-def _sample_chunk(B, N, H, S):
-    """_score_chunk for the sampler's workspace."""
-    sc = S
-    while sc > 1:
-        nbytes = N_.order_sample_workspace(B, N, H, sc)
-        if 0 < nbytes <= SCORE_WS_CAP:
-            return sc, nbytes
-        sc = (sc + 1) // 2
-    return 1, N_.order_sample_workspace(B, N, H, 1)
-
-
 @torch.no_grad()
 def sample_orders_batch(args, model, enc, samples, seed, stream_id=0, return_steps=False):
     """`samples` ancestral samples from the pointer decoder for every story of an encode() tuple
@@ -1087,13 +1046,12 @@ def sample_orders_batch(args, model, enc, samples, seed, stream_id=0, return_ste
     (seed, stream_id, b, s) only: the first S' of S samples are the samples of a call for S'.
     S is split like score_orders_batch's K to keep the workspace within SCORE_WS_CAP. An
     unsupported shape (N > 16) raises _native.Unsupported: there is no host sampler."""
-    (sent, _p, dec_init, okeys, _cls, cls_mat, _cs, cs_mat, _h1, _h2) = enc
-    B, N, H = sent.shape
+    B, N, H = enc[0].shape
     S = int(samples)
     if S < 1:
         raise ValueError(f"samples must be >= 1, got {samples}")
-    dev = sent.device
-    sc, nbytes = _sample_chunk(B, N, H, S)
+    dev = enc[0].device
+    sc, nbytes = _fit_chunk(lambda s: N_.order_sample_workspace(B, N, H, s), S)
     if nbytes == 0:
         raise N_.Unsupported(f"sample_orders_batch: B={B} N={N} H={H} S={S} is outside "
                              "mmseq_order_sample's limits")
@@ -1103,17 +1061,10 @@ def sample_orders_batch(args, model, enc, samples, seed, stream_id=0, return_ste
     if return_steps:
         u = torch.empty(B, S, max(N - 1, 0), dtype=torch.float32, device=dev)
         steps = torch.empty(B, S, max(N - 1, 0), N, dtype=torch.float32, device=dev)
-    hist = torch.cat([cls_mat, torch.softmax(cs_mat, -1)], -1).contiguous()
-    ins = (sent.contiguous(), okeys.contiguous(), hist, dec_init[0][0].contiguous(),
-           dec_init[1][0].contiguous(), [model.store.f32(n) for n in _BEAM_WEIGHTS])
-    cache = model.__dict__.setdefault("_score_ws", {})
-    for s0 in range(0, S, sc):
-        s = min(sc, S - s0)
+    ins = _decoder_inputs(model, enc)[3]
+    for s0, s, whole in K._chunks(S, sc):
         nb = nbytes if s == sc else N_.order_sample_workspace(B, N, H, s)
-        ws = cache.get((B, N, H, s))  # the scorer's layout: one cache serves both
-        if ws is None or ws.numel() * 4 < nb:
-            ws = cache[(B, N, H, s)] = torch.empty(nb // 4, dtype=torch.float32, device=dev)
-        whole = s == S
+        ws = K._cached_ws(model, "_score_ws", (B, N, H, s), nb, dev)  # the scorer's layout and cache
         o_c = orders if whole else torch.empty(B, s, N, dtype=torch.int64, device=dev)
         n_c = nll if whole else torch.empty(B, s, dtype=torch.float32, device=dev)
         u_c = st_c = None

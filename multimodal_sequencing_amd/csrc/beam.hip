@@ -9,13 +9,8 @@
 // host. The dense parts run over all B*W rows through mmseq_gemm; rows of slots >= nb hold
 // whatever the workspace held and are never read by another row.
 //
-// pw_k is linear, so the four blocks of its input are projected ONCE per story:
-//   PROJ[g][b][i][j][:] = pw_k.weight[:, g(H+2):(g+1)(H+2)] hist[b][i][j]        g = 0..3
-//   keys[j] = PROJ[0][l1][j] + PROJ[1][l2][j] + (sum_{j'} m PROJ[2][j][j']) / N
-//                                             + (sum_{i}  m PROJ[3][i][j]) / N
-// with m = (i != j, neither pointed). Likewise x W_ih^T + b_ih for x = doc[b][i] is one GEMM.
-//
-// Two more entries run the same setup and the same step (beam_story_setup, beam_step):
+// The per-call setup and the step itself (GX, PROJ, cell, query, pointer energies) are
+// pointer_decoder.h's. Every other entry here runs that setup and the same step (beam_step):
 // mmseq_beam_search_nbest reports every finished hypothesis of the last selection, and
 // mmseq_order_score runs K candidate orders per story as slots that never branch (W = nb = K,
 // every slot entered with score 0) and, instead of selecting, adds each slot's own pick to its nll.
@@ -24,19 +19,16 @@
 // mmseq_order_tree scores ALL N! orders: the prefix tree walked level by level in chunks
 // (order_tree_plan.h), a chunk being a beam of W = nb = cnt slots per story whose children enter
 // with their parent's s entry, so that every shared prefix is stepped once.
-#include "common.h"
 #include "order_tree_plan.h"
+#include "pointer_decoder.h"
 
 namespace {
 
-constexpr int BEAM_MAXN = 16;
 constexpr int BEAM_MAXW = 32;
 
 struct BeamWs {  // float offsets into the workspace, each a multiple of 4 (16-byte rows)
   int64_t gx, proj, h[2], c[2], gh, q, s, score[2], seq[2], total;
 };
-
-inline int64_t up4(int64_t n) { return (n + 3) / 4 * 4; }
 
 BeamWs beam_layout(int B, int N, int H, int W) {
   BeamWs w;
@@ -112,8 +104,6 @@ __global__ __launch_bounds__(256) void beam_init_kernel(int N, int H, int W,
   if (threadIdx.x == 0) score[slot] = 0.f;
 }
 
-__device__ __forceinline__ float bsigm(float x) { return 1.f / (1.f + expf(-x)); }
-
 // LSTM cell (gates i, f, g, o) of the live slots, in place: x W_ih^T + b_ih is row `last` of the
 // story's GX (t > 0) or b_ih alone (t = 0, x = 0); gh already holds h W_hh^T + b_hh.
 __global__ __launch_bounds__(256) void beam_cell_kernel(int H, int W, int N, int t, int nb,
@@ -128,13 +118,9 @@ __global__ __launch_bounds__(256) void beam_cell_kernel(int H, int W, int N, int
   const float* x = t > 0 ? gx + ((int64_t)b * N + seq[slot * BEAM_MAXN + t - 1]) * 4 * H : b_ih;
   const float* g4 = gh + slot * 4 * H;
   for (int u = threadIdx.x; u < H; u += 256) {
-    const float i = bsigm(x[u] + g4[u]);
-    const float f = bsigm(x[H + u] + g4[H + u]);
-    const float g = tanhf(x[2 * H + u] + g4[2 * H + u]);
-    const float o = bsigm(x[3 * H + u] + g4[3 * H + u]);
-    const float c2 = f * c[slot * H + u] + i * g;
-    c[slot * H + u] = c2;
-    h[slot * H + u] = o * tanhf(c2);
+    const LstmCell r = lstm_cell(x, g4, H, u, c + slot * H + u);
+    c[slot * H + u] = r.c2;
+    h[slot * H + u] = r.h;
   }
 }
 
@@ -245,9 +231,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(int N, int H, int W, i
           have |= 1u << v;
         }
         order[(int64_t)b * N + t] = j;
-        int miss = 0;
-        while ((have >> miss) & 1u) ++miss;  // length N - 1 < N entries: one index is always free
-        order[(int64_t)b * N + t + 1] = miss;
+        order[(int64_t)b * N + t + 1] = lowest_free(have);  // N - 1 < N entries: one is free
         best[b] = sh_s[i];
       }
       if (nbest.orders) {
@@ -267,9 +251,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(int N, int H, int W, i
           int64_t* o = nbest.orders + ((int64_t)b * W + cnt) * N;
           for (int p = 0; p < t; ++p) o[p] = seq_cur[(slot0 + w) * BEAM_MAXN + p];
           o[t] = j;
-          int miss = 0;
-          while ((have >> miss) & 1u) ++miss;
-          o[t + 1] = miss;
+          o[t + 1] = lowest_free(have);
           nbest.scores[(int64_t)b * W + cnt] = sh_s[i];
           ++cnt;
         }
@@ -316,15 +298,7 @@ __global__ __launch_bounds__(256) void order_init_kernel(int N, int H, int K,
     return;
   }
   const int64_t* cand = orders + (int64_t)b * story_stride + (int64_t)k * N;
-  unsigned have = 0;
-  bool ok = true;
-  for (int p = 0; p < N - 1; ++p) {  // every thread: the same N - 1 loads, no LDS, no barrier
-    const int64_t v = cand[p];
-    const bool in = v >= 0 && v < N;
-    const unsigned bit = in ? 1u << (int)v : 0u;
-    ok = ok && in && !(have & bit);
-    have |= bit;
-  }
+  const bool ok = candidate_ok(cand, N);
   const int p = threadIdx.x;
   if (p < N - 1) seq[slot * BEAM_MAXN + p] = ok ? (int)cand[p] : p;
   if (threadIdx.x == 0) {
@@ -397,8 +371,7 @@ __global__ __launch_bounds__(256) void sample_pick_kernel(int64_t R, int N, int 
   const uint32_t lo = (sample0 + smp) * (uint32_t)(N - 1) + (uint32_t)t, hi = story0 + b;
   const uint32_t h = drop_mix(drop_mix(lo ^ k0) + (hi ^ k1));
   const float u = (float)(h >> 8) * 0x1p-24f;
-  unsigned pointed = 0;
-  for (int p = 0; p < t; ++p) pointed |= 1u << seq[slot * BEAM_MAXN + p];
+  const unsigned pointed = pointed_mask(seq + slot * BEAM_MAXN, t);
   const float* row = s + slot * N;
   float total = 0.f;
   for (int j = 0; j < N; ++j)
@@ -417,10 +390,7 @@ __global__ __launch_bounds__(256) void sample_pick_kernel(int64_t R, int N, int 
   nll[slot] += row[pick];
   orders[slot * N + t] = pick;
   if (t == N - 2) {  // the last position is the one step left
-    const unsigned have = pointed | (1u << pick);
-    int miss = 0;
-    while ((have >> miss) & 1u) ++miss;
-    orders[slot * N + N - 1] = miss;
+    orders[slot * N + N - 1] = lowest_free(pointed | (1u << pick));
   }
   if (u_out) u_out[slot * (N - 1) + t] = u;
   if (step_nlp)
@@ -439,44 +409,21 @@ inline bool score_supported(int B, int N, int H, int K) {
          (int64_t)B * K * BEAM_MAXN < INT32_MAX;
 }
 
-struct BeamWeights {
-  const float *w_ih, *b_ih, *w_hh, *b_hh, *w_q, *b_q, *w_pw, *w_t, *b_t;
-};
-
-mmseq_status beam_gemm(int M, int Nn, int K, const float* A, int64_t lda, const float* Bm,
-                       int64_t ldb, float* C, const float* bias, mmseq_stream stream) {
-  return mmseq_gemm(0, M, Nn, K, 1, A, lda, 0, Bm, ldb, 0, C, Nn, 0, bias, MMSEQ_ACT_NONE, nullptr,
-                    nullptr, nullptr, 0, 0, 1.0f, 0, MMSEQ_F32, MMSEQ_F32, nullptr, MMSEQ_GEMM_AUTO,
-                    nullptr, 0, stream);
-}
-
-// once per call: the input gates of every sentence (GX) and the four projections of hist (PROJ)
-mmseq_status beam_story_setup(int B, int N, int H, const float* doc, const float* hist,
-                              const BeamWeights& wt, float* gx, float* proj, int64_t pstride,
-                              mmseq_stream stream) {
-  mmseq_status e;
-  if (N > 2 && (e = beam_gemm(B * N, 4 * H, H, doc, H, wt.w_ih, H, gx, wt.b_ih, stream)) != MMSEQ_OK)
-    return e;
-  for (int g = 0; g < 4; ++g)
-    if ((e = beam_gemm(B * N * N, H, H + 2, hist, H + 2, wt.w_pw + (int64_t)g * (H + 2),
-                       4 * (int64_t)(H + 2), proj + g * pstride, nullptr, stream)) != MMSEQ_OK)
-      return e;
-  return MMSEQ_OK;
-}
-
 // step t of R = B*W slots, nb of them live per story: LSTM cell in place, query, s = score - logp
-mmseq_status beam_step(int B, int N, int H, int W, int t, int nb, const BeamWeights& wt,
+mmseq_status beam_step(int B, int N, int H, int W, int t, int nb, const DecoderWeights& wt,
                        const float* okey, const float* gx, const float* proj, int64_t pstride,
                        const int* seq, const float* score, float* h, float* c, float* gh, float* q,
                        float* s, mmseq_stream stream) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int R = B * W;
   mmseq_status e;
-  if ((e = beam_gemm(R, 4 * H, H, h, H, wt.w_hh, H, gh, wt.b_hh, stream)) != MMSEQ_OK) return e;
+  const GemmSlab none{nullptr, 0};
+  if ((e = dec_gemm(R, 4 * H, H, h, H, wt.w_hh, H, gh, 4 * H, wt.b_hh, 0, none, stream)) != MMSEQ_OK)
+    return e;
   hipLaunchKernelGGL(beam_cell_kernel, dim3(R), dim3(256), 0, st, H, W, N, t, nb, gx, wt.b_ih, gh,
                      seq, h, c);
   if ((e = mmseq_check_launch("beam_cell")) != MMSEQ_OK) return e;
-  if ((e = beam_gemm(R, H, H, h, H, wt.w_q, H, q, wt.b_q, stream)) != MMSEQ_OK) return e;
+  if ((e = dec_gemm(R, H, H, h, H, wt.w_q, H, q, H, wt.b_q, 0, none, stream)) != MMSEQ_OK) return e;
   hipLaunchKernelGGL(beam_score_kernel, dim3(R), dim3(256), 0, st, N, H, W, t, nb, q, proj, pstride,
                      okey, wt.w_t, wt.b_t, seq, score, s);
   return mmseq_check_launch("beam_score");
@@ -485,22 +432,19 @@ mmseq_status beam_step(int B, int N, int H, int W, int t, int nb, const BeamWeig
 // mmseq_beam_search (order / score) and mmseq_beam_search_nbest (nbest) are this one decode
 mmseq_status beam_run(const char* what, int B, int N, int H, int W, const float* doc,
                       const float* okey, const float* hist, const float* h0, const float* c0,
-                      const BeamWeights& wt, int64_t* order, float* score, NBest nbest,
+                      const DecoderWeights& wt, int64_t* order, float* score, NBest nbest,
                       void* workspace, int64_t workspace_bytes, mmseq_stream stream) {
   if (!beam_supported(B, N, H, W))
     return mmseq_set_error(MMSEQ_EUNSUPPORTED,
                            "%s: B=%d N=%d H=%d W=%d outside 1 <= N <= %d, 1 <= W <= %d "
                            "(or B*W*N / H too large for 32-bit row counts)",
                            what, B, N, H, W, BEAM_MAXN, BEAM_MAXW);
-  MMSEQ_REQUIRE(doc && okey && hist && h0 && c0 && wt.w_ih && wt.b_ih && wt.w_hh && wt.b_hh &&
-                    wt.w_q && wt.b_q && wt.w_pw && wt.w_t && wt.b_t &&
-                    ((order && score) || (nbest.orders && nbest.scores && nbest.count)),
-                "%s: null buffer", what);
   const BeamWs L = beam_layout(B, N, H, W);
-  MMSEQ_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= L.total * 4,
-                "%s: workspace must be 16-byte aligned and hold %lld bytes (got %lld)", what,
-                (long long)(L.total * 4), (long long)workspace_bytes);
-  if (B == 0) return MMSEQ_OK;
+  mmseq_status e = decoder_require(
+      what, doc, okey, hist, h0, c0, wt,
+      (order && score) || (nbest.orders && nbest.scores && nbest.count), "", workspace,
+      workspace_bytes, L.total * 4);
+  if (e != MMSEQ_OK || B == 0) return e;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   float* ws = reinterpret_cast<float*>(workspace);
   float* hb[2] = {ws + L.h[0], ws + L.h[1]};
@@ -509,10 +453,10 @@ mmseq_status beam_run(const char* what, int B, int N, int H, int W, const float*
   int* sq[2] = {reinterpret_cast<int*>(ws + L.seq[0]), reinterpret_cast<int*>(ws + L.seq[1])};
   hipLaunchKernelGGL(beam_init_kernel, dim3(B), dim3(256), 0, st, N, H, W, h0, c0, hb[0], cb[0],
                      sc[0], order, score, nbest);
-  mmseq_status e = mmseq_check_launch("beam_init");
+  e = mmseq_check_launch("beam_init");
   if (e != MMSEQ_OK || N == 1) return e;
   const int64_t pstride = up4((int64_t)B * N * N * H);
-  if ((e = beam_story_setup(B, N, H, doc, hist, wt, ws + L.gx, ws + L.proj, pstride, stream)) !=
+  if ((e = story_setup(B, N, H, doc, hist, wt, ws + L.gx, ws + L.proj, pstride, stream)) !=
       MMSEQ_OK)
     return e;
   int nb = 1;
@@ -586,8 +530,7 @@ __global__ __launch_bounds__(256) void tree_expand_kernel(int N, int H, int t, i
   const int fan = N - t + 1;
   const int64_t prow = b * pcnt + (i / fan - pbase);
   const int r = (int)(i % fan);
-  unsigned pointed = 0;
-  for (int p = 0; p < t - 1; ++p) pointed |= 1u << pseq[prow * BEAM_MAXN + p];
+  const unsigned pointed = pointed_mask(pseq + prow * BEAM_MAXN, t - 1);
   const int pick = tree_nth_free(pointed, r);
   if ((int)threadIdx.x < t - 1)
     seq[slot * BEAM_MAXN + threadIdx.x] = pseq[prow * BEAM_MAXN + threadIdx.x];
@@ -622,8 +565,7 @@ __global__ __launch_bounds__(256) void tree_leaf_kernel(int64_t R, int N, int64_
   const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (slot >= R) return;
   const int64_t b = slot / cnt, i = base + slot % cnt;
-  unsigned pointed = 0;
-  for (int p = 0; p < N - 2; ++p) pointed |= 1u << seq[slot * BEAM_MAXN + p];
+  const unsigned pointed = pointed_mask(seq + slot * BEAM_MAXN, N - 2);
   const int j0 = tree_nth_free(pointed, 0), j1 = tree_nth_free(pointed | (1u << j0), 0);
   nll[b * leaves + 2 * i] = s[slot * N + j0];
   nll[b * leaves + 2 * i + 1] = s[slot * N + j1];
@@ -670,7 +612,7 @@ extern "C" mmseq_status mmseq_beam_search(int B, int N, int H, int W, const floa
                                           void* workspace, int64_t workspace_bytes,
                                           mmseq_stream stream) {
   return beam_run("beam_search", B, N, H, W, doc, okey, hist, h0, c0,
-                  BeamWeights{w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t}, order, score,
+                  DecoderWeights{w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t}, order, score,
                   NBest{nullptr, nullptr, nullptr}, workspace, workspace_bytes, stream);
 }
 
@@ -684,7 +626,7 @@ extern "C" mmseq_status mmseq_beam_search_nbest(int B, int N, int H, int W, cons
                                                 float* scores, int32_t* count, void* workspace,
                                                 int64_t workspace_bytes, mmseq_stream stream) {
   return beam_run("beam_search_nbest", B, N, H, W, doc, okey, hist, h0, c0,
-                  BeamWeights{w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t}, nullptr, nullptr,
+                  DecoderWeights{w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t}, nullptr, nullptr,
                   NBest{orders, scores, count}, workspace, workspace_bytes, stream);
 }
 
@@ -707,17 +649,15 @@ extern "C" mmseq_status mmseq_order_score(int B, int N, int H, int K, const floa
                            "order_score: B=%d N=%d H=%d K=%d outside 1 <= N <= %d, 1 <= K, "
                            "B*K*4H < 2^31 (or B / H too large for 32-bit row counts)",
                            B, N, H, K, BEAM_MAXN);
-  MMSEQ_REQUIRE(doc && okey && hist && h0 && c0 && w_ih && b_ih && w_hh && b_hh && w_q && b_q &&
-                    w_pw && w_t && b_t && orders && nll,
-                "order_score: null buffer");
-  MMSEQ_REQUIRE(story_stride == 0 || story_stride >= (int64_t)K * N,
-                "order_score: story_stride %lld is neither 0 (shared list) nor >= K*N",
-                (long long)story_stride);
+  char why[DEC_WHY] = "";
+  if (!(story_stride == 0 || story_stride >= (int64_t)K * N))
+    snprintf(why, sizeof why, "story_stride %lld is neither 0 (shared list) nor >= K*N",
+             (long long)story_stride);
+  const DecoderWeights wt{w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t};
   const ScoreWs L = score_layout(B, N, H, K);
-  MMSEQ_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= L.total * 4,
-                "order_score: workspace must be 16-byte aligned and hold %lld bytes (got %lld)",
-                (long long)(L.total * 4), (long long)workspace_bytes);
-  if (B == 0) return MMSEQ_OK;
+  mmseq_status e = decoder_require("order_score", doc, okey, hist, h0, c0, wt, orders && nll, why,
+                                   workspace, workspace_bytes, L.total * 4);
+  if (e != MMSEQ_OK || B == 0) return e;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   float* ws = reinterpret_cast<float*>(workspace);
   const int R = B * K;
@@ -725,11 +665,10 @@ extern "C" mmseq_status mmseq_order_score(int B, int N, int H, int K, const floa
   int* bad = reinterpret_cast<int*>(ws + L.bad);
   hipLaunchKernelGGL(order_init_kernel, dim3(R), dim3(256), 0, st, N, H, K, orders, story_stride,
                      h0, c0, ws + L.h, ws + L.c, ws + L.zero, seq, bad, nll, step_nll);
-  mmseq_status e = mmseq_check_launch("order_init");
+  e = mmseq_check_launch("order_init");
   if (e != MMSEQ_OK || N == 1) return e;
-  const BeamWeights wt{w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t};
   const int64_t pstride = up4((int64_t)B * N * N * H);
-  if ((e = beam_story_setup(B, N, H, doc, hist, wt, ws + L.gx, ws + L.proj, pstride, stream)) !=
+  if ((e = story_setup(B, N, H, doc, hist, wt, ws + L.gx, ws + L.proj, pstride, stream)) !=
       MMSEQ_OK)
     return e;
   for (int t = 0; t < N - 1; ++t) {  // every slot is live (nb = K) and enters with score 0
@@ -763,31 +702,28 @@ extern "C" mmseq_status mmseq_order_sample(int B, int N, int H, int S, const flo
                            "order_sample: B=%d N=%d H=%d S=%d outside 1 <= N <= %d, 1 <= S, "
                            "B*S*4H < 2^31 (or B / H too large for 32-bit row counts)",
                            B, N, H, S, BEAM_MAXN);
-  MMSEQ_REQUIRE(doc && okey && hist && h0 && c0 && w_ih && b_ih && w_hh && b_hh && w_q && b_q &&
-                    w_pw && w_t && b_t && orders && nll,
-                "order_sample: null buffer");
-  MMSEQ_REQUIRE(story0 >= 0 && sample0 >= 0 && (int64_t)story0 + B < INT32_MAX &&
-                    ((int64_t)sample0 + S) * BEAM_MAXN < INT32_MAX,
-                "order_sample: story0 %d / sample0 %d negative or beyond the 32-bit counter words",
-                story0, sample0);
+  char why[DEC_WHY] = "";
+  if (!(story0 >= 0 && sample0 >= 0 && (int64_t)story0 + B < INT32_MAX &&
+        ((int64_t)sample0 + S) * BEAM_MAXN < INT32_MAX))
+    snprintf(why, sizeof why, "story0 %d / sample0 %d negative or beyond the 32-bit counter words",
+             story0, sample0);
   const ScoreWs L = score_layout(B, N, H, S);  // the scorer's layout; its `bad` row is not used
-  MMSEQ_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= L.total * 4,
-                "order_sample: workspace must be 16-byte aligned and hold %lld bytes (got %lld)",
-                (long long)(L.total * 4), (long long)workspace_bytes);
-  if (B == 0) return MMSEQ_OK;
+  const DecoderWeights wt{w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t};
+  mmseq_status e = decoder_require("order_sample", doc, okey, hist, h0, c0, wt, orders && nll, why,
+                                   workspace, workspace_bytes, L.total * 4);
+  if (e != MMSEQ_OK || B == 0) return e;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   float* ws = reinterpret_cast<float*>(workspace);
   const int R = B * S;
   int* seq = reinterpret_cast<int*>(ws + L.seq);
   hipLaunchKernelGGL(sample_init_kernel, dim3(R), dim3(256), 0, st, N, H, S, h0, c0, ws + L.h,
                      ws + L.c, ws + L.zero, orders, nll);
-  mmseq_status e = mmseq_check_launch("sample_init");
+  e = mmseq_check_launch("sample_init");
   if (e != MMSEQ_OK || N == 1) return e;
   const mmseq_dropout key = {0.5f, stream_id, seed};  // the dropout key schedule; p is not used
   const Drop d = make_drop(&key);
-  const BeamWeights wt{w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t};
   const int64_t pstride = up4((int64_t)B * N * N * H);
-  if ((e = beam_story_setup(B, N, H, doc, hist, wt, ws + L.gx, ws + L.proj, pstride, stream)) !=
+  if ((e = story_setup(B, N, H, doc, hist, wt, ws + L.gx, ws + L.proj, pstride, stream)) !=
       MMSEQ_OK)
     return e;
   for (int t = 0; t < N - 1; ++t) {  // every slot is live (nb = S) and enters with score 0
@@ -821,19 +757,17 @@ extern "C" mmseq_status mmseq_order_tree(int B, int N, int H, const float* doc, 
                            "order_tree: B=%d N=%d H=%d outside 1 <= N <= %d, B*N! < 2^31, "
                            "B*N*4H < 2^31 (or B / H beyond the beam's limits)",
                            B, N, H, order_tree::MAXN);
-  MMSEQ_REQUIRE(doc && okey && hist && h0 && c0 && w_ih && b_ih && w_hh && b_hh && w_q && b_q &&
-                    w_pw && w_t && b_t && nll,
-                "order_tree: null buffer");
-  MMSEQ_REQUIRE(rows >= (int64_t)B * N, "order_tree: rows %lld below B*N = %lld", (long long)rows,
-                (long long)B * N);
   order_tree::Plan P;
-  MMSEQ_REQUIRE(order_tree::make_plan(B, N, H, rows, &P), "order_tree: no plan for rows %lld",
-                (long long)rows);
-  MMSEQ_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= P.total * 4,
-                "order_tree: workspace must be 16-byte aligned and hold %lld bytes (got %lld)",
-                (long long)(P.total * 4), (long long)workspace_bytes);
+  char why[DEC_WHY] = "";
+  if (rows < (int64_t)B * N)
+    snprintf(why, sizeof why, "rows %lld below B*N = %lld", (long long)rows, (long long)B * N);
+  else if (!order_tree::make_plan(B, N, H, rows, &P))
+    snprintf(why, sizeof why, "no plan for rows %lld", (long long)rows);
+  const DecoderWeights wt{w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t};
+  mmseq_status e = decoder_require("order_tree", doc, okey, hist, h0, c0, wt, nll != nullptr, why,
+                                   workspace, workspace_bytes, why[0] ? 0 : P.total * 4);
+  if (e != MMSEQ_OK) return e;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  mmseq_status e;
   if (orders) {
     hipLaunchKernelGGL(tree_unrank_kernel, dim3((unsigned)((P.leaves + 255) / 256)), dim3(256), 0,
                        st, P.leaves, N, orders);
@@ -844,8 +778,7 @@ extern "C" mmseq_status mmseq_order_tree(int B, int N, int H, const float* doc, 
   hipLaunchKernelGGL(tree_root_kernel, dim3(B), dim3(256), 0, st, N, H, h0, c0, ws + P.lv[0].h,
                      ws + P.lv[0].c, ws + P.lv[0].score, nll);
   if ((e = mmseq_check_launch("tree_root")) != MMSEQ_OK || N == 1) return e;
-  const BeamWeights wt{w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t};
-  if ((e = beam_story_setup(B, N, H, doc, hist, wt, ws + P.gx, ws + P.proj, P.pstride, stream)) !=
+  if ((e = story_setup(B, N, H, doc, hist, wt, ws + P.gx, ws + P.proj, P.pstride, stream)) !=
       MMSEQ_OK)
     return e;
   e = MMSEQ_OK;

@@ -2,7 +2,7 @@
 // encoder output, the pointer-network scoring + masked log-softmax + NLL, and the small
 // multi-head attention of the inter-sentence encoder. All fp32 compute; no host loops, no
 // device->host syncs (the reference does 2P .cpu() syncs + ~6P scalar index_put per step here).
-#include "common.h"
+#include "pointer_decoder.h"
 
 namespace {
 
@@ -355,8 +355,7 @@ __global__ __launch_bounds__(256) void small_attn_bwd_kernel(int B, int T, int h
 // ------------------------------------------------------------------------------------------------
 // LSTM cell (modeling_bert.py:1027-1078 nn.LSTM decoder, gate order i, f, g, o), one thread per
 // (row, unit): gates = gx + gh (both already include their biases); saves the four activations.
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-
+// The cell and its backward are pointer_decoder.h's.
 __global__ __launch_bounds__(256) void lstm_fwd_kernel(int B, int H, const float* __restrict__ gx,
                                                        int64_t ldx, const float* __restrict__ gh,
                                                        const float* __restrict__ c,
@@ -367,19 +366,14 @@ __global__ __launch_bounds__(256) void lstm_fwd_kernel(int B, int H, const float
   if (idx >= (int64_t)B * H) return;
   const int b = (int)(idx / H), u = (int)(idx - (int64_t)b * H);
   const float* x = gx + b * ldx;
-  const float* hh = gh + (int64_t)b * 4 * H;
-  const float i = sigm(x[u] + hh[u]);
-  const float f = sigm(x[H + u] + hh[H + u]);
-  const float g = tanhf(x[2 * H + u] + hh[2 * H + u]);
-  const float o = sigm(x[3 * H + u] + hh[3 * H + u]);
-  const float c2 = f * c[idx] + i * g;
-  c_out[idx] = c2;
-  h_out[idx] = o * tanhf(c2);
+  const LstmCell r = lstm_cell(x, gh + (int64_t)b * 4 * H, H, u, c + idx);
+  c_out[idx] = r.c2;
+  h_out[idx] = r.h;
   float* a = act + (int64_t)b * 4 * H;
-  a[u] = i;
-  a[H + u] = f;
-  a[2 * H + u] = g;
-  a[3 * H + u] = o;
+  a[u] = r.i;
+  a[H + u] = r.f;
+  a[2 * H + u] = r.g;
+  a[3 * H + u] = r.o;
 }
 
 // dh, dc_next (gradient flowing into c_out) -> dgates (pre-activation) and dc_prev
@@ -394,16 +388,15 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(int B, int H, const float
   if (idx >= (int64_t)B * H) return;
   const int b = (int)(idx / H), u = (int)(idx - (int64_t)b * H);
   const float* a = act + (int64_t)b * 4 * H;
-  const float i = a[u], f = a[H + u], g = a[2 * H + u], o = a[3 * H + u];
-  const float tc = tanhf(c_out[idx]);
-  const float dhv = dh ? dh[idx] : 0.f;
-  const float dc = (dc_next ? dc_next[idx] : 0.f) + dhv * o * (1.f - tc * tc);
+  const LstmCellGrad r =
+      lstm_cell_bwd(a[u], a[H + u], a[2 * H + u], a[3 * H + u], c[idx], c_out[idx],
+                    dh ? dh[idx] : 0.f, dc_next ? dc_next[idx] : 0.f);
   float* d = dgates + (int64_t)b * 4 * H;
-  d[u] = dc * g * i * (1.f - i);
-  d[H + u] = dc * c[idx] * f * (1.f - f);
-  d[2 * H + u] = dc * i * (1.f - g * g);
-  d[3 * H + u] = dhv * tc * o * (1.f - o);
-  dc_prev[idx] = dc * f;
+  d[u] = r.di;
+  d[H + u] = r.df;
+  d[2 * H + u] = r.dg;
+  d[3 * H + u] = r.d_o;
+  dc_prev[idx] = r.dc_prev;
 }
 
 extern "C" mmseq_status mmseq_pointer_fwd(int B, int N, int H, const float* q, const float* key,

@@ -2,10 +2,9 @@
 // the encoder output (doc, okey, hist, h0, c0) and the nine decoder weights, for sequence-level
 // losses over a candidate list (include/mmseq.h).
 //
-// The entry recomputes the scorer's forward itself (the ABI keeps no state between calls) with the
-// scorer's formulation: R = B*K slots that never branch, x W_ih^T + b_ih for every sentence from
-// ONE GEMM (GX), the four blocks of pw_k projected ONCE per story (PROJ). It keeps h_t, c_t and the
-// gate activations of every step in its workspace and then runs
+// The entry recomputes the scorer's forward itself (the ABI keeps no state between calls) through
+// pointer_decoder.h's setup and step, the code the scorer runs: R = B*K slots that never branch.
+// It keeps h_t, c_t and the gate activations of every step in its workspace and then runs
 //   1. one launch over all (slot, step): e, softmax, de, dA = de w_t (1 - a^2) per key, dq, and
 //      the slot's partial rows of dw_t / db_t (a step's pointer part depends on the LSTM chain
 //      only through q_t, so the steps need no order here),
@@ -15,15 +14,12 @@
 //      slot's seq row. Nothing is scattered and there is no atomic anywhere: every sum has one
 //      owner and one order, so two calls give the same bits,
 //   4. the dense parts through mmseq_gemm / mmseq_gemm_wgrad (fp32, fixed-order split-K).
-#include "common.h"
+#include "pointer_decoder.h"
 
 namespace {
 
-constexpr int OG_MAXN = 16;           // seq row stride, the beam's BEAM_MAXN
 constexpr int OG_CS_ROWS = 64;        // rows per partial of the two-level column sum
 constexpr int64_t OG_SLAB = 1 << 20;  // floats of split-K scratch handed to the GEMMs
-
-inline int64_t up4(int64_t n) { return (n + 3) / 4 * 4; }
 
 struct GradWs {  // float offsets, each a multiple of 4
   int64_t gx, proj, hs, cs, gates, q, dA, wpart, dh, dc, csum, slab, seq, bad, total;
@@ -47,7 +43,7 @@ GradWs grad_layout(int B, int N, int H, int K) {
   w.dc = o; o += up4(R * H);
   w.csum = o; o += up4((T * R + OG_CS_ROWS - 1) / OG_CS_ROWS * 4 * H);
   w.slab = o; o += OG_SLAB;
-  w.seq = o; o += up4(R * OG_MAXN);               // int32 picks
+  w.seq = o; o += up4(R * BEAM_MAXN);               // int32 picks
   w.bad = o; o += up4(R);                         // int32, 1 = invalid candidate
   w.total = o;
   return w;
@@ -55,17 +51,15 @@ GradWs grad_layout(int B, int N, int H, int K) {
 
 // mmseq_order_score's limits (every offset into the stacked per-step rows is 64-bit)
 inline bool grad_supported(int B, int N, int H, int K) {
-  if (!(B >= 0 && N >= 1 && N <= OG_MAXN && H >= 1 && K >= 1)) return false;
-  if (!((int64_t)B * 32 * OG_MAXN * 4 < INT32_MAX / 2 && (int64_t)H * 4 * 4 < INT32_MAX / 2))
+  if (!(B >= 0 && N >= 1 && N <= BEAM_MAXN && H >= 1 && K >= 1)) return false;
+  if (!((int64_t)B * 32 * BEAM_MAXN * 4 < INT32_MAX / 2 && (int64_t)H * 4 * 4 < INT32_MAX / 2))
     return false;
-  return (int64_t)B * K * 4 * H < INT32_MAX && (int64_t)B * K * OG_MAXN < INT32_MAX;
+  return (int64_t)B * K * 4 * H < INT32_MAX && (int64_t)B * K * BEAM_MAXN < INT32_MAX;
 }
 
-__device__ __forceinline__ float gsigm(float x) { return 1.f / (1.f + expf(-x)); }
-
-// One workgroup per slot (story b, candidate k): order_init_kernel's validation (every entry is
-// checked BEFORE any forms an address; an invalid candidate runs as 0, 1, .., N-2 and is marked
-// bad), h_0 / c_0 rows <- (h0, c0).
+// One workgroup per slot (story b, candidate k): the candidate is validated before any of its
+// entries forms an address (an invalid one runs as 0, 1, .., N-2 and is marked bad), h_0 / c_0
+// rows <- (h0, c0).
 __global__ __launch_bounds__(256) void og_init_kernel(int N, int H, int K,
                                                       const int64_t* __restrict__ orders,
                                                       int64_t story_stride,
@@ -76,17 +70,9 @@ __global__ __launch_bounds__(256) void og_init_kernel(int N, int H, int K,
   const int64_t slot = blockIdx.x;
   const int b = (int)(slot / K), k = (int)(slot % K);
   const int64_t* cand = orders + (int64_t)b * story_stride + (int64_t)k * N;
-  unsigned have = 0;
-  bool ok = true;
-  for (int p = 0; p < N - 1; ++p) {
-    const int64_t v = cand[p];
-    const bool in = v >= 0 && v < N;
-    const unsigned bit = in ? 1u << (int)v : 0u;
-    ok = ok && in && !(have & bit);
-    have |= bit;
-  }
+  const bool ok = candidate_ok(cand, N);
   const int p = threadIdx.x;
-  if (p < OG_MAXN) seq[slot * OG_MAXN + p] = p < N - 1 ? (ok ? (int)cand[p] : p) : 0;
+  if (p < BEAM_MAXN) seq[slot * BEAM_MAXN + p] = p < N - 1 ? (ok ? (int)cand[p] : p) : 0;
   if (threadIdx.x == 0) bad[slot] = ok ? 0 : 1;
   for (int u = threadIdx.x; u < H; u += 256) {
     h[slot * H + u] = h0[(int64_t)b * H + u];
@@ -94,7 +80,7 @@ __global__ __launch_bounds__(256) void og_init_kernel(int N, int H, int K,
   }
 }
 
-// beam_cell_kernel's cell of step t that keeps its state: `g4` enters as h W_hh^T + b_hh and leaves
+// The cell of step t that keeps its state: `g4` enters as h W_hh^T + b_hh and leaves
 // as the gate activations (i, f, g, o); (h, c) of step t -> rows of step t + 1.
 __global__ __launch_bounds__(256) void og_cell_kernel(int H, int K, int N, int t,
                                                       const float* __restrict__ gx,
@@ -106,22 +92,19 @@ __global__ __launch_bounds__(256) void og_cell_kernel(int H, int K, int N, int t
                                                       float* __restrict__ c_out) {
   const int64_t slot = blockIdx.x;
   const int b = (int)(slot / K);
-  const float* x = t > 0 ? gx + ((int64_t)b * N + seq[slot * OG_MAXN + t - 1]) * 4 * H : b_ih;
+  const float* x = t > 0 ? gx + ((int64_t)b * N + seq[slot * BEAM_MAXN + t - 1]) * 4 * H : b_ih;
   float* g4 = g4all + slot * 4 * H;
   for (int u = threadIdx.x; u < H; u += 256) {
-    const float i = gsigm(x[u] + g4[u]);
-    const float f = gsigm(x[H + u] + g4[H + u]);
-    const float g = tanhf(x[2 * H + u] + g4[2 * H + u]);
-    const float o = gsigm(x[3 * H + u] + g4[3 * H + u]);
-    const float c2 = f * c_in[slot * H + u] + i * g;
-    g4[u] = i; g4[H + u] = f; g4[2 * H + u] = g; g4[3 * H + u] = o;
-    c_out[slot * H + u] = c2;
-    h_out[slot * H + u] = o * tanhf(c2);
+    const LstmCell r = lstm_cell(x, g4, H, u, c_in + slot * H + u);
+    g4[u] = r.i; g4[H + u] = r.f; g4[2 * H + u] = r.g; g4[3 * H + u] = r.o;
+    c_out[slot * H + u] = r.c2;
+    h_out[slot * H + u] = r.h;
   }
 }
 
 // One workgroup per (step t, slot). First beam_score_kernel's forward (one wave per key j, the
-// same sums in the same order) with a_t[j] = tanh(q + key + okey) kept in the dA rows; then
+// same sums in the same order: the loop is kept as a second copy) with
+// a_t[j] = tanh(q + key + okey) kept in the dA rows; then
 //   de[j] = G (p[j] - [j = y_t]) for j not pointed, exactly 0 where pointed (G = 0 for a bad slot)
 //           with p[y_t] - 1 taken as -sum_{j != y_t} p[j]
 //   dA[j][u] = de[j] w_t[u] (1 - a[j][u]^2),  dq[u] = sum_j dA[j][u] (j ascending, over q in place)
@@ -139,17 +122,17 @@ __global__ __launch_bounds__(256) void og_score_bwd_kernel(int N, int H, int K, 
                                                            const float* __restrict__ dnll,
                                                            float* __restrict__ dA,
                                                            float* __restrict__ wpart) {
-  __shared__ float e[OG_MAXN];
+  __shared__ float e[BEAM_MAXN];
   const int64_t row = blockIdx.x;  // t * R + slot
   const int t = (int)(row / R);
   const int64_t slot = row % R;
   const int b = (int)(slot / K);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned pointed = 0;
-  for (int p = 0; p < t; ++p) pointed |= 1u << seq[slot * OG_MAXN + p];
-  const int l1 = t > 0 ? seq[slot * OG_MAXN + t - 1] : 0;
-  const int l2 = t > 1 ? seq[slot * OG_MAXN + t - 2] : 0;
-  const int y = seq[slot * OG_MAXN + t];
+  for (int p = 0; p < t; ++p) pointed |= 1u << seq[slot * BEAM_MAXN + p];
+  const int l1 = t > 0 ? seq[slot * BEAM_MAXN + t - 1] : 0;
+  const int l2 = t > 1 ? seq[slot * BEAM_MAXN + t - 2] : 0;
+  const int y = seq[slot * BEAM_MAXN + t];
   const float* P1 = proj;
   const float* P2 = proj + proj_stride;
   const float* PF = proj + 2 * proj_stride;
@@ -191,23 +174,23 @@ __global__ __launch_bounds__(256) void og_score_bwd_kernel(int N, int H, int K, 
   const float G = bad[slot] ? 0.f : dnll[slot];
   // de of the pick as minus the sum of the others (p_y - 1 = -sum_{j != y} p_j): no cancellation
   // where p_y is close to 1, and the step's logit gradients sum to zero as they do analytically
-  float de[OG_MAXN];
+  float de[BEAM_MAXN];
   float others = 0.f;
 #pragma unroll
-  for (int j = 0; j < OG_MAXN; ++j) {
+  for (int j = 0; j < BEAM_MAXN; ++j) {
     const bool live = j < N && j != y && !((pointed >> j) & 1u);
     de[j] = live ? G * (expf(e[j] - mx) / sum) : 0.f;
     others += de[j];
   }
 #pragma unroll
-  for (int j = 0; j < OG_MAXN; ++j)
+  for (int j = 0; j < BEAM_MAXN; ++j)
     if (j == y) de[j] = -others;
   float* wp = wpart + row * (H + 1);
   for (int u = threadIdx.x; u < H; u += 256) {
     const float w = wt[u];
     float dq = 0.f, dw = 0.f;
 #pragma unroll
-    for (int j = 0; j < OG_MAXN; ++j) {
+    for (int j = 0; j < BEAM_MAXN; ++j) {
       if (j < N) {
         const float a = ar[(int64_t)j * H + u];
         dw += de[j] * a;
@@ -222,9 +205,9 @@ __global__ __launch_bounds__(256) void og_score_bwd_kernel(int N, int H, int K, 
   if (threadIdx.x == 0) {
     float db = 0.f;  // the others ascending, then the pick
 #pragma unroll
-    for (int j = 0; j < OG_MAXN; ++j) db += j == y ? 0.f : de[j];
+    for (int j = 0; j < BEAM_MAXN; ++j) db += j == y ? 0.f : de[j];
 #pragma unroll
-    for (int j = 0; j < OG_MAXN; ++j) db += j == y ? de[j] : 0.f;
+    for (int j = 0; j < BEAM_MAXN; ++j) db += j == y ? de[j] : 0.f;
     wp[H] = db;
   }
 }
@@ -240,15 +223,13 @@ __global__ __launch_bounds__(256) void og_cell_bwd_kernel(int64_t n, int H, floa
   const int64_t r = idx / H;
   const int u = (int)(idx - r * H);
   float* a = act + r * 4 * H;
-  const float i = a[u], f = a[H + u], g = a[2 * H + u], o = a[3 * H + u];
-  const float tc = tanhf(c_out[idx]);
-  const float dhv = dh[idx];
-  const float dc = (dc_in ? dc_in[idx] : 0.f) + dhv * o * (1.f - tc * tc);
-  a[u] = dc * g * i * (1.f - i);
-  a[H + u] = dc * c[idx] * f * (1.f - f);
-  a[2 * H + u] = dc * i * (1.f - g * g);
-  a[3 * H + u] = dhv * tc * o * (1.f - o);
-  dc_out[idx] = dc * f;
+  const LstmCellGrad d = lstm_cell_bwd(a[u], a[H + u], a[2 * H + u], a[3 * H + u], c[idx],
+                                       c_out[idx], dh[idx], dc_in ? dc_in[idx] : 0.f);
+  a[u] = d.di;
+  a[H + u] = d.df;
+  a[2 * H + u] = d.dg;
+  a[3 * H + u] = d.d_o;
+  dc_out[idx] = d.dc_prev;
 }
 
 // One workgroup per story: dh0[b] = sum_k dh[b, k], dc0 likewise, k ascending.
@@ -283,7 +264,7 @@ __global__ __launch_bounds__(256) void og_gather_gx_kernel(int N, int H, int K, 
     for (int k = 0; k < K; ++k) {
       const int64_t slot = (int64_t)b * K + k;
       for (int t = 1; t < N - 1; ++t)
-        if (seq[slot * OG_MAXN + t - 1] == i) acc += dgates[((int64_t)t * R + slot) * H4 + u];
+        if (seq[slot * BEAM_MAXN + t - 1] == i) acc += dgates[((int64_t)t * R + slot) * H4 + u];
     }
     dgx[bi * H4 + u] = acc;
   }
@@ -308,7 +289,7 @@ __global__ __launch_bounds__(256) void og_gather_key_kernel(int N, int H, int K,
     float p0 = 0.f, p1 = 0.f, m = 0.f, all = 0.f;
     for (int k = 0; k < K; ++k) {
       const int64_t slot = b * K + k;
-      const int* sq = seq + slot * OG_MAXN;
+      const int* sq = seq + slot * BEAM_MAXN;
       unsigned pointed = 0;
       for (int t = 0; t < N - 1; ++t) {
         const bool c0 = t > 0 && sq[t - 1] == i;
@@ -372,19 +353,10 @@ mmseq_status og_colsum(int64_t rows, int cols, const float* x, int64_t ldx, floa
   return mmseq_check_launch("order_score_bwd colsum");
 }
 
-// C[M][Nn] (+)= A[M][K] B[Nn][K]^T (+ bias), fp32, split-K scratch from the workspace
-mmseq_status og_gemm(int M, int Nn, int K, const float* A, int64_t lda, const float* Bm, int64_t ldb,
-                     float* C, int64_t ldc, const float* bias, int accumulate, float* slab,
-                     mmseq_stream stream) {
-  return mmseq_gemm(0, M, Nn, K, 1, A, lda, 0, Bm, ldb, 0, C, ldc, 0, bias, MMSEQ_ACT_NONE, nullptr,
-                    nullptr, nullptr, 0, 0, 1.0f, accumulate, MMSEQ_F32, MMSEQ_F32, nullptr,
-                    MMSEQ_GEMM_AUTO, slab, slab ? OG_SLAB * 4 : 0, stream);
-}
-
 mmseq_status og_wgrad(int M, int Nn, int K, const float* A, int64_t lda, const float* Bm,
-                      int64_t ldb, float* C, int64_t ldc, float* slab, mmseq_stream stream) {
+                      int64_t ldb, float* C, int64_t ldc, GemmSlab slab, mmseq_stream stream) {
   return mmseq_gemm_wgrad(M, Nn, K, A, lda, Bm, ldb, C, ldc, nullptr, MMSEQ_F32, MMSEQ_GEMM_AUTO,
-                          slab, OG_SLAB * 4, stream);
+                          slab.ptr, slab.bytes, stream);
 }
 
 }  // namespace
@@ -416,22 +388,20 @@ extern "C" mmseq_status mmseq_order_score_bwd(
     return mmseq_set_error(MMSEQ_EUNSUPPORTED,
                            "order_score_bwd: B=%d N=%d H=%d K=%d outside 1 <= N <= %d, 1 <= K, "
                            "B*K*4H < 2^31 (or B / H too large for 32-bit row counts)",
-                           B, N, H, K, OG_MAXN);
-  MMSEQ_REQUIRE(doc && okey && hist && h0 && c0 && w_ih && b_ih && w_hh && b_hh && w_q && b_q &&
-                    w_pw && w_t && b_t && wt_ih && wt_hh && wt_q && wt_pw && orders && dnll &&
-                    ddoc && dokey && dhist && dh0 && dc0 && dw_ih && db_ih && dw_hh && db_hh &&
-                    dw_q && db_q && dw_pw && dw_t && db_t,
-                "order_score_bwd: null buffer");
-  MMSEQ_REQUIRE(story_stride == 0 || story_stride >= (int64_t)K * N,
-                "order_score_bwd: story_stride %lld is neither 0 (shared list) nor >= K*N",
-                (long long)story_stride);
+                           B, N, H, K, BEAM_MAXN);
+  char why[DEC_WHY] = "";
+  if (!(story_stride == 0 || story_stride >= (int64_t)K * N))
+    snprintf(why, sizeof why, "story_stride %lld is neither 0 (shared list) nor >= K*N",
+             (long long)story_stride);
+  const DecoderWeights wt{w_ih, b_ih, w_hh, b_hh, w_q, b_q, w_pw, w_t, b_t};
   const GradWs L = grad_layout(B, N, H, K);
-  MMSEQ_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= L.total * 4,
-                "order_score_bwd: workspace must be 16-byte aligned and hold %lld bytes (got %lld)",
-                (long long)(L.total * 4), (long long)workspace_bytes);
-  if (B == 0) return MMSEQ_OK;
+  mmseq_status e = decoder_require(
+      "order_score_bwd", doc, okey, hist, h0, c0, wt,
+      wt_ih && wt_hh && wt_q && wt_pw && orders && dnll && ddoc && dokey && dhist && dh0 && dc0 &&
+          dw_ih && db_ih && dw_hh && db_hh && dw_q && db_q && dw_pw && dw_t && db_t,
+      why, workspace, workspace_bytes, L.total * 4);
+  if (e != MMSEQ_OK || B == 0) return e;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  mmseq_status e;
   const int64_t BN = (int64_t)B * N;
   if (N == 1) {  // no step: the scores are constants
     OG_HIP(hipMemsetAsync(ddoc, 0, BN * H * 4, st));
@@ -448,24 +418,22 @@ extern "C" mmseq_status mmseq_order_score_bwd(
   int* bad = reinterpret_cast<int*>(ws + L.bad);
   float *gx = ws + L.gx, *proj = ws + L.proj, *hs = ws + L.hs, *cs = ws + L.cs;
   float *gates = ws + L.gates, *q = ws + L.q, *dA = ws + L.dA, *wpart = ws + L.wpart;
-  float *dh = ws + L.dh, *dc = ws + L.dc, *csum = ws + L.csum, *slab = ws + L.slab;
+  float *dh = ws + L.dh, *dc = ws + L.dc, *csum = ws + L.csum;
+  const GemmSlab slab{ws + L.slab, OG_SLAB * 4}, none{nullptr, 0};  // split-K scratch
 
   // ---- forward, keeping every step's state -----------------------------------------------------
   hipLaunchKernelGGL(og_init_kernel, dim3(R), dim3(256), 0, st, N, H, K, orders, story_stride, h0,
                      c0, hs, cs, seq, bad);
   OG_TRY(mmseq_check_launch("order_score_bwd init"));
-  if (N > 2) OG_TRY(og_gemm((int)BN, H4, H, doc, H, w_ih, H, gx, H4, b_ih, 0, nullptr, stream));
-  for (int g = 0; g < 4; ++g)
-    OG_TRY(og_gemm((int)(BN * N), H, H2, hist, H2, w_pw + (int64_t)g * H2, 4 * (int64_t)H2,
-                   proj + g * L.pstride, H, nullptr, 0, nullptr, stream));
+  OG_TRY(story_setup(B, N, H, doc, hist, wt, gx, proj, L.pstride, stream));
   for (int t = 0; t < T; ++t) {
     float* gt = gates + t * RH4;
-    OG_TRY(og_gemm(R, H4, H, hs + t * RH, H, w_hh, H, gt, H4, b_hh, 0, nullptr, stream));
+    OG_TRY(dec_gemm(R, H4, H, hs + t * RH, H, w_hh, H, gt, H4, b_hh, 0, none, stream));
     hipLaunchKernelGGL(og_cell_kernel, dim3(R), dim3(256), 0, st, H, K, N, t, gx, b_ih, seq, gt,
                        cs + t * RH, hs + (t + 1) * RH, cs + (t + 1) * RH);
     OG_TRY(mmseq_check_launch("order_score_bwd cell"));
     // per step, as the scorer runs it: the same rows give the same q bits
-    OG_TRY(og_gemm(R, H, H, hs + (t + 1) * RH, H, w_q, H, q + t * RH, H, b_q, 0, nullptr, stream));
+    OG_TRY(dec_gemm(R, H, H, hs + (t + 1) * RH, H, w_q, H, q + t * RH, H, b_q, 0, none, stream));
   }
 
   // ---- 1. the pointer part of every (step, slot) -----------------------------------------------
@@ -477,12 +445,12 @@ extern "C" mmseq_status mmseq_order_score_bwd(
   const int64_t n = RH;
   for (int t = T - 1; t >= 0; --t) {
     float* gt = gates + t * RH4;
-    OG_TRY(og_gemm(R, H, H, q + t * RH, H, wt_q, H, dh, H, nullptr, t == T - 1 ? 0 : 1, slab,
+    OG_TRY(dec_gemm(R, H, H, q + t * RH, H, wt_q, H, dh, H, nullptr, t == T - 1 ? 0 : 1, slab,
                    stream));
     hipLaunchKernelGGL(og_cell_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, H,
                        gt, cs + t * RH, cs + (t + 1) * RH, dh, t == T - 1 ? nullptr : dc, dc);
     OG_TRY(mmseq_check_launch("order_score_bwd cell_bwd"));
-    OG_TRY(og_gemm(R, H, H4, gt, H4, wt_hh, H4, dh, H, nullptr, 0, slab, stream));
+    OG_TRY(dec_gemm(R, H, H4, gt, H4, wt_hh, H4, dh, H, nullptr, 0, slab, stream));
   }
   hipLaunchKernelGGL(og_gather_state_kernel, dim3(B), dim3(256), 0, st, H, K, dh, dc, dh0, dc0);
   OG_TRY(mmseq_check_launch("order_score_bwd gather_state"));
@@ -500,7 +468,7 @@ extern "C" mmseq_status mmseq_order_score_bwd(
   // ---- 4. dense parts ----------------------------------------------------------------------------
   const int64_t TR = (int64_t)T * R;
   if (N > 2) {
-    OG_TRY(og_gemm((int)BN, H, H4, gx, H4, wt_ih, H4, ddoc, H, nullptr, 0, slab, stream));
+    OG_TRY(dec_gemm((int)BN, H, H4, gx, H4, wt_ih, H4, ddoc, H, nullptr, 0, slab, stream));
     OG_TRY(og_wgrad(H4, H, (int)BN, gx, H4, doc, H, dw_ih, H, slab, stream));
   } else {
     OG_HIP(hipMemsetAsync(ddoc, 0, BN * H * 4, st));
@@ -510,7 +478,7 @@ extern "C" mmseq_status mmseq_order_score_bwd(
   OG_TRY(og_wgrad(H, H, (int)TR, q, H, hs + RH, H, dw_q, H, slab, stream));
   OG_TRY(og_colsum(TR, H, q, H, csum, db_q, nullptr, st));
   for (int g = 0; g < 4; ++g) {
-    OG_TRY(og_gemm((int)(BN * N), H2, H, proj + g * L.pstride, H, wt_pw + (int64_t)g * H2 * H, H,
+    OG_TRY(dec_gemm((int)(BN * N), H2, H, proj + g * L.pstride, H, wt_pw + (int64_t)g * H2 * H, H,
                    dhist, H2, nullptr, g > 0, slab, stream));
     OG_TRY(og_wgrad(H, H2, (int)(BN * N), proj + g * L.pstride, H, hist, H2,
                     dw_pw + (int64_t)g * H2, 4 * (int64_t)H2, slab, stream));

@@ -985,25 +985,28 @@ ORDER_WEIGHTS_T = ("decoder.weight_ih_l0", "decoder.weight_hh_l0", "query_linear
                    "pw_k.weight")
 
 
-def order_grad_chunk(B, Nn, H, Kn, cap):
-    """-> (candidates per call, bytes): the largest count, halving from Kn, whose
-    mmseq_order_score_bwd workspace fits `cap` bytes (a single candidate is always tried);
-    bytes 0 = unsupported shape."""
-    kc = Kn
-    while kc > 1:
-        nbytes = N.order_score_bwd_workspace(B, Nn, H, kc)
-        if 0 < nbytes <= cap:
-            return kc, nbytes
-        kc = (kc + 1) // 2
-    return 1, N.order_score_bwd_workspace(B, Nn, H, 1)
+def _chunks(n, step):
+    """n items in chunks of `step` -> (start, length, whole); whole: the one chunk is all n."""
+    for i0 in range(0, n, step):
+        k = min(step, n - i0)
+        yield i0, k, k == n
 
 
-def _order_ws(store, nbytes, device):
-    """One workspace per store, grown on demand: it serves the forward and the backward."""
-    ws = getattr(store, "_order_grad_ws", None)
+def _cached_ws(owner, slot, key, nbytes, device):
+    """The f32 workspace `owner` keeps under (slot, key), allocated where there is none and again
+    where the one kept is too small or on another device (so a slot with one key grows on
+    demand). Used by berson's decoder entries too."""
+    cache = owner.__dict__.setdefault(slot, {})
+    ws = cache.get(key)
     if ws is None or ws.numel() * 4 < nbytes or ws.device != device:
-        ws = store._order_grad_ws = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+        ws = cache[key] = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
     return ws
+
+
+def order_grad_chunk(B, Nn, H, Kn, cap):
+    """-> (candidates per call, bytes) of mmseq_order_score_bwd under `cap` bytes."""
+    from .berson import _fit_chunk  # berson imports this module
+    return _fit_chunk(lambda k: N.order_score_bwd_workspace(B, Nn, H, k), Kn, cap=cap)
 
 
 class OrderScoreFn(torch.autograd.Function):
@@ -1024,12 +1027,12 @@ class OrderScoreFn(torch.autograd.Function):
         if nbytes == 0 or N.order_score_workspace(B, Nn, H, kc) == 0:
             raise N.Unsupported(f"OrderScoreFn: B={B} N={Nn} H={H} K={Kn} is outside "
                                 "mmseq_order_score's limits")
-        ws = _order_ws(store, max(nbytes, N.order_score_workspace(B, Nn, H, kc)), doc.device)
+        # one workspace per store, grown on demand: it serves the forward and the backward
+        ws = _cached_ws(store, "_order_grad_ws", None,
+                        max(nbytes, N.order_score_workspace(B, Nn, H, kc)), doc.device)
         weights = [store.f32(n) for n in ORDER_WEIGHTS]
         nll = torch.empty(B, Kn, dtype=torch.float32, device=doc.device)
-        for k0 in range(0, Kn, kc):
-            k = min(kc, Kn - k0)
-            whole = k == Kn
+        for k0, k, whole in _chunks(Kn, kc):
             o_c = orders if whole else orders[..., k0:k0 + k, :].contiguous()
             n_c = nll if whole else torch.empty(B, k, dtype=torch.float32, device=doc.device)
             N._check_shape(N.order_score(doc, okey, hist, h0, c0, weights, o_c, n_c, None, ws),
@@ -1051,12 +1054,11 @@ class OrderScoreFn(torch.autograd.Function):
         weights = [store.f32(n) for n in ORDER_WEIGHTS]
         weights_t = [store.wt(n) for n in ORDER_WEIGHTS_T]
         dweights = [store.g(n) for n in ORDER_WEIGHTS]
-        ws = _order_ws(store, N.order_score_bwd_workspace(B, Nn, H, kc), doc.device)
+        ws = _cached_ws(store, "_order_grad_ws", None, N.order_score_bwd_workspace(B, Nn, H, kc),
+                        doc.device)
         dnll = dnll.contiguous().float()
         total = None
-        for k0 in range(0, Kn, kc):
-            k = min(kc, Kn - k0)
-            whole = k == Kn
+        for k0, k, whole in _chunks(Kn, kc):
             o_c = orders if whole else orders[..., k0:k0 + k, :].contiguous()
             g_c = dnll if whole else dnll[:, k0:k0 + k].contiguous()
             dins = [torch.empty_like(t) for t in (doc, okey, hist, h0, c0)]
