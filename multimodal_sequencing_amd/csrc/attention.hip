@@ -15,9 +15,12 @@
 //            dK^T += Q^T dS take P / dS straight from the accumulators.
 //      dq:   per query tile, sweep the keys with the swapped form; dQ^T += K^T dS^T.
 #include "gemm_common.h"
+#include "launch_plan.h"
 #include <type_traits>
 
 namespace {
+
+using namespace mmseq_plan;  // grids, LDS bytes and kernel choice of the bf16 fast kernels
 
 constexpr int HD = 64;       // head dim
 constexpr int QT = 64;       // rows per workgroup tile
@@ -2162,17 +2165,6 @@ __global__ __launch_bounds__(256, FOLD || DMODE == 1 ? 2 : 3) void attn_dkdv_bf1
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-// Row blocks of the tail-folding kernels: T = 128 n + r with 1 <= r <= 16 (T = 513, 393, 769 on the
-// path) runs n blocks, the last one also owning the r tail rows, instead of n + 1 blocks whose last
-// has one active wave; a block's time is set by its key sweep, not by how many of its rows are valid
-// (DESIGN §7), so the n + 1-th block cost a full block.
-void tail_fold(AttnArgs& a, int T) {  // T = 0: no fold (a.nxq from a.T)
-  const int n = T / 128, r = T % 128;
-  const bool fold = n >= 1 && r >= 1 && r <= 16;
-  a.tail0 = fold ? n * 128 : 0;
-  a.nxq = fold ? n : (a.T + 127) / 128;
-}
-
 mmseq_status check_common(int P, int T, int heads, const void* qkv, int64_t ld, int64_t qo,
                           int64_t ko, int64_t vo, mmseq_dtype dt) {
   MMSEQ_REQUIRE(P >= 0 && T > 0 && heads > 0, "attn: bad sizes P=%d T=%d heads=%d", P, T, heads);
@@ -2183,6 +2175,41 @@ mmseq_status check_common(int P, int T, int heads, const void* qkv, int64_t ld, 
   MMSEQ_REQUIRE(qo + heads * 64 <= ld && ko + heads * 64 <= ld && vo + heads * 64 <= ld,
                 "attn: head slices exceed the row");
   return MMSEQ_OK;
+}
+
+// the fields every entry fills alike; each adds its own outputs
+AttnArgs attn_args(int P, int T, int Tq, int heads, const void* qkv, int64_t ld_qkv, int64_t q_off,
+                   int64_t k_off, int64_t v_off, const float* key_bias, float scale,
+                   const mmseq_dropout* drop, const uint64_t* keep_bits) {
+  AttnArgs a = {};
+  a.P = P; a.T = T; a.Tq = Tq; a.heads = heads; a.qkv = qkv; a.ld_qkv = ld_qkv;
+  a.q_off = q_off; a.k_off = k_off; a.v_off = v_off; a.key_bias = key_bias; a.scale = scale;
+  a.drop = make_drop(drop);
+  a.bits = const_cast<uint64_t*>(keep_bits);  // read and written by the bf16 fast kernels alone
+  a.nkt2 = attn_nkt2(T);
+  return a;
+}
+
+// bf16 fast kernels by [dmode][wide or fold]. Without dropout there is no pair index, so dmode 0
+// has the narrow form only; the counter-hash dK/dV never folds.
+typedef void (*AttnKernel)(AttnArgs);
+typedef const AttnKernel FwdFamily[3][2];
+FwdFamily FWD32 = {{attn_fwd32_kernel<0, false>, attn_fwd32_kernel<0, false>},
+                   {attn_fwd32_kernel<1, false>, attn_fwd32_kernel<1, true>},
+                   {attn_fwd32_kernel<2, false>, attn_fwd32_kernel<2, true>}};
+FwdFamily FWD16 = {{attn_fwd_bf16_kernel<0, false>, attn_fwd_bf16_kernel<0, false>},
+                   {attn_fwd_bf16_kernel<1, false>, attn_fwd_bf16_kernel<1, true>},
+                   {attn_fwd_bf16_kernel<2, false>, attn_fwd_bf16_kernel<2, true>}};
+FwdFamily FWD16_Q8 = {{attn_fwd_bf16_kernel<0, false, true>, attn_fwd_bf16_kernel<0, false, true>},
+                      {attn_fwd_bf16_kernel<1, false, true>, attn_fwd_bf16_kernel<1, true, true>},
+                      {attn_fwd_bf16_kernel<2, false, true>, attn_fwd_bf16_kernel<2, true, true>}};
+const AttnKernel DQ16[3] = {attn_dq_bf16_kernel<0>, attn_dq_bf16_kernel<1>, attn_dq_bf16_kernel<2>};
+const AttnKernel DKDV16[3][2] = {{attn_dkdv_bf16_kernel<0, false>, attn_dkdv_bf16_kernel<0, true>},
+                                 {attn_dkdv_bf16_kernel<1, false>, nullptr},
+                                 {attn_dkdv_bf16_kernel<2, false>, attn_dkdv_bf16_kernel<2, true>}};
+
+void launch_fwd(FwdFamily& k, const AttnFwdPlan& p, const AttnArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(k[p.dmode][p.wide], dim3(p.blocks), dim3(p.threads), (size_t)p.lds_bytes, s, a);
 }
 
 }  // namespace
@@ -2198,46 +2225,14 @@ static mmseq_status attn_fwd_impl(int P, int T, int Tq, int heads, const void* q
   MMSEQ_REQUIRE(Tq >= 1 && Tq <= T && (Tq == T || (dtype == MMSEQ_BF16 && variant == 1)),
                 "attn_fwd: Tq=%d (1 <= Tq <= T; Tq < T needs the bf16 variant-1 kernels)", Tq);
   if (P == 0) return MMSEQ_OK;
-  AttnArgs a = {};
-  a.P = P; a.T = T; a.Tq = Tq; a.heads = heads; a.qkv = qkv; a.ld_qkv = ld_qkv;
-  a.q_off = q_off; a.k_off = k_off; a.v_off = v_off; a.key_bias = key_bias; a.scale = scale;
+  AttnArgs a = attn_args(P, T, Tq, heads, qkv, ld_qkv, q_off, k_off, v_off, key_bias, scale, drop, keep_bits);
   a.o_w = out; a.ld_out = ld_out; a.lse = lse;
-  a.drop = make_drop(drop);
   dim3 grid((T + QT - 1) / QT, heads, P);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == MMSEQ_BF16 && variant == 2) {
+  if (dtype == MMSEQ_BF16 && variant) {
     MMSEQ_REQUIRE(aligned16(out) && ld_out % 8 == 0, "attn_fwd: out must be 16-byte aligned rows");
-    const dim3 gq((unsigned)(((T + 127) / 128) * heads * P));
-    const int nkt = (T + 63) / 64;
-    const size_t lds = (size_t)4 * 4096 * 2 + (size_t)nkt * (64 + 1) * 4;
-    a.bits = keep_bits;
-    a.nkt2 = (nkt + 1) & ~1;
-    // largest dropout pair index + the in-tile key offset must stay below 2^32 for the narrow path
-    const bool wide = ((uint64_t)P * heads * T * (uint64_t)((T + 3) & ~3)) / 4 + 64 >= (1ull << 32);
-    if (a.drop.thr && keep_bits)
-      hipLaunchKernelGGL((wide ? attn_fwd32_kernel<2, true> : attn_fwd32_kernel<2, false>), gq,
-                         dim3(128), lds, s, a);
-    else if (a.drop.thr)
-      hipLaunchKernelGGL((wide ? attn_fwd32_kernel<1, true> : attn_fwd32_kernel<1, false>), gq,
-                         dim3(128), lds, s, a);
-    else
-      hipLaunchKernelGGL((attn_fwd32_kernel<0, false>), gq, dim3(128), lds, s, a);
-  } else if (dtype == MMSEQ_BF16 && variant) {
-    MMSEQ_REQUIRE(aligned16(out) && ld_out % 8 == 0, "attn_fwd: out must be 16-byte aligned rows");
-    const dim3 gq((unsigned)(((Tq + 127) / 128) * heads * P));
-    const size_t lds = (size_t)4 * 4096 * 2 + (size_t)((T + 63) / 64) * (64 + 1) * 4;
-    a.bits = keep_bits;
-    a.nkt2 = (((T + 63) / 64) + 1) & ~1;
-    // largest dropout pair index + the in-tile key offset must stay below 2^32 for the narrow path
-    const bool wide = ((uint64_t)P * heads * T * (uint64_t)((T + 3) & ~3)) / 4 + 64 >= (1ull << 32);
-    if (a.drop.thr && keep_bits)
-      hipLaunchKernelGGL((wide ? attn_fwd_bf16_kernel<2, true> : attn_fwd_bf16_kernel<2, false>), gq,
-                         dim3(256), lds, s, a);
-    else if (a.drop.thr)
-      hipLaunchKernelGGL((wide ? attn_fwd_bf16_kernel<1, true> : attn_fwd_bf16_kernel<1, false>), gq,
-                         dim3(256), lds, s, a);
-    else
-      hipLaunchKernelGGL((attn_fwd_bf16_kernel<0, false>), gq, dim3(256), lds, s, a);
+    launch_fwd(variant == 2 ? FWD32 : FWD16,
+               attn_fwd_plan(P, T, Tq, heads, variant, a.drop.thr != 0, keep_bits != nullptr), a, s);
   } else if (dtype == MMSEQ_BF16)
     hipLaunchKernelGGL(attn_fwd_kernel<unsigned short>, grid, dim3(256), 0, s, a);
   else
@@ -2288,12 +2283,9 @@ static mmseq_status attn_bwd_impl(int P, int T, int Tq, int heads, const void* q
   MMSEQ_REQUIRE(Tq >= 1 && Tq <= T && (Tq == T || (dtype == MMSEQ_BF16 && variant && !q8)),
                 "attn_bwd: Tq=%d (1 <= Tq <= T; Tq < T needs the bf16 fast kernels, no MX-fp8 copy)", Tq);
   if (P == 0) return MMSEQ_OK;
-  AttnArgs a = {};
-  a.P = P; a.T = T; a.Tq = Tq; a.heads = heads; a.qkv = qkv; a.ld_qkv = ld_qkv;
-  a.q_off = q_off; a.k_off = k_off; a.v_off = v_off; a.key_bias = key_bias; a.scale = scale;
+  AttnArgs a = attn_args(P, T, Tq, heads, qkv, ld_qkv, q_off, k_off, v_off, key_bias, scale, drop, keep_bits);
   a.out = out; a.ld_out = ld_out; a.dout = dout; a.ld_dout = ld_dout;
   a.lse = const_cast<float*>(lse); a.delta = delta; a.dqkv = dqkv; a.ld_dqkv = ld_dqkv;
-  a.drop = make_drop(drop);
   a.q8 = reinterpret_cast<uint8_t*>(q8); a.ldq8 = ldq8; a.q8s = reinterpret_cast<uint8_t*>(q8_scales);
   if (q8 && !(dtype == MMSEQ_BF16 && variant))
     return mmseq_set_error(MMSEQ_EUNSUPPORTED, "attn_bwd_mxfp8: the bf16 fast kernels only");
@@ -2304,46 +2296,18 @@ static mmseq_status attn_bwd_impl(int P, int T, int Tq, int heads, const void* q
   if (dtype == MMSEQ_BF16 && variant) {
     MMSEQ_REQUIRE(aligned16(out) && ld_out % 8 == 0 && aligned16(dqkv) && ld_dqkv % 8 == 0,
                   "attn_bwd: out / dqkv must be 16-byte aligned rows");
-    const dim3 gq((unsigned)(((T + 127) / 128) * heads * P));
-    const size_t lds = (size_t)4 * 4096 * 2 + (size_t)((T + 63) / 64) * 64 * 4 * 2 + 2048;
-    // dQ: K / V double buffer + the key-bias row (four workgroups per CU without dropout)
-    const size_t ldsq = (size_t)4 * 4096 * 2 + (size_t)((T + 63) / 64) * 64 * 4;
-    a.bits = const_cast<uint64_t*>(keep_bits);
-    a.nkt2 = (((T + 63) / 64) + 1) & ~1;
-    // dK/dV tail fold: + the tail keys' keep words (2 KB) and K / V fragments (4 KB); the counter-
-    // hash mode (no keep bits) runs unfolded (its registers are spent on the hashed keep masks)
-    const int dmode = a.drop.thr ? (keep_bits ? 2 : 1) : 0;
+    // dQ, then dK/dV in up to two launches: the blocks without the tail keys, and the tail block
+    // (x = nplain) with the fold's state and LDS
+    const AttnBwdPlan bp = attn_bwd_plan(P, T, Tq, heads, a.drop.thr != 0, keep_bits != nullptr);
+    hipLaunchKernelGGL(DQ16[bp.dmode], dim3(bp.dq_blocks), dim3(256), (size_t)bp.dq_lds, s, a);
     AttnArgs ak = a;
-    tail_fold(ak, dmode == 1 ? 0 : T);
-    const size_t ldsk = lds + (ak.tail0 ? 6144 : 0);
-    // the dQ kernel does not fold: its tail state took it from three to two waves per SIMD
-    // (148 -> 236 VGPRs), slower at T = 513 and 393 than the extra block it saves
-    tail_fold(a, 0);
-    const dim3 gdq((unsigned)(((Tq + 127) / 128) * heads * P));
-    // dK/dV: the blocks without the tail keys in one launch, the tail blocks (x = nxq - 1 when
-    // folded) in a second one with the fold's state and LDS
-    const int nplain = ak.tail0 ? ak.nxq - 1 : ak.nxq;
-    AttnArgs akt = ak;
-    ak.xoff = 0; ak.nxl = nplain;
-    akt.xoff = nplain; akt.nxl = 1;
-    const dim3 gdk((unsigned)(nplain * heads * P)), gdt((unsigned)(heads * P));
-    const int ntail = ak.tail0 ? 1 : 0;
-#define DKDV_PLAIN(D) if (nplain) hipLaunchKernelGGL((attn_dkdv_bf16_kernel<D, false>), gdk, dim3(256), lds, s, ak)
-#define DKDV_TAIL(D) if (ntail) hipLaunchKernelGGL((attn_dkdv_bf16_kernel<D, true>), gdt, dim3(256), ldsk, s, akt)
-    if (dmode == 2) {
-      hipLaunchKernelGGL(attn_dq_bf16_kernel<2>, gdq, dim3(256), ldsq, s, a);
-      DKDV_PLAIN(2);
-      DKDV_TAIL(2);
-    } else if (dmode == 1) {
-      hipLaunchKernelGGL(attn_dq_bf16_kernel<1>, gdq, dim3(256), ldsq, s, a);
-      DKDV_PLAIN(1);  // the counter-hash mode never folds
-    } else {
-      hipLaunchKernelGGL(attn_dq_bf16_kernel<0>, gdq, dim3(256), ldsq, s, a);
-      DKDV_PLAIN(0);
-      DKDV_TAIL(0);
-    }
-#undef DKDV_PLAIN
-#undef DKDV_TAIL
+    ak.tail0 = bp.tail0; ak.nxq = bp.nxq;
+    ak.xoff = 0; ak.nxl = bp.nplain;
+    if (bp.nplain)
+      hipLaunchKernelGGL(DKDV16[bp.dmode][0], dim3(bp.plain_blocks), dim3(256), (size_t)bp.dkdv_lds, s, ak);
+    ak.xoff = bp.nplain; ak.nxl = 1;
+    if (bp.ntail)
+      hipLaunchKernelGGL(DKDV16[bp.dmode][1], dim3(bp.tail_blocks), dim3(256), (size_t)bp.tail_lds, s, ak);
   } else if (dtype == MMSEQ_BF16) {
     hipLaunchKernelGGL(attn_delta_kernel<unsigned short>, gd, dim3(256), 0, s, a);
     hipLaunchKernelGGL(attn_dkdv_kernel<unsigned short>, grid, dim3(256), 0, s, a);
@@ -2398,8 +2362,7 @@ extern "C" mmseq_status mmseq_attn_bwd_mxfp8(int P, int T, int heads, const void
 }
 
 extern "C" int64_t mmseq_attn_keep_bits_words(int P, int T, int heads) {
-  const int64_t nkt2 = (((T + 63) / 64) + 1) & ~1;
-  return (int64_t)P * heads * T * nkt2;
+  return keep_bits_words(P, T, heads);
 }
 
 extern "C" mmseq_status mmseq_attn_fwd_mxfp8_dual(int P, int T, int heads, const void* qkv,
@@ -2417,27 +2380,11 @@ extern "C" mmseq_status mmseq_attn_fwd_mxfp8_dual(int P, int T, int heads, const
   MMSEQ_REQUIRE(!out || (ld_out >= heads * 64 && ld_out % 4 == 0 && ((uintptr_t)out & 7) == 0),
                 "attn_fwd_mxfp8: bf16 out must be 8-byte aligned rows");
   if (P == 0) return MMSEQ_OK;
-  AttnArgs a = {};
-  a.P = P; a.T = T; a.Tq = T; a.heads = heads; a.qkv = qkv; a.ld_qkv = ld_qkv;
-  a.q_off = q_off; a.k_off = k_off; a.v_off = v_off; a.key_bias = key_bias; a.scale = scale;
-  a.lse = lse; a.drop = make_drop(drop);
-  a.o_w = out; a.ld_out = ld_out;
+  AttnArgs a = attn_args(P, T, T, heads, qkv, ld_qkv, q_off, k_off, v_off, key_bias, scale, drop, keep_bits);
+  a.lse = lse; a.o_w = out; a.ld_out = ld_out;
   a.q8 = reinterpret_cast<uint8_t*>(q8); a.ldq8 = ldq8; a.q8s = reinterpret_cast<uint8_t*>(q8_scales);
-  const dim3 gq((unsigned)(((T + 127) / 128) * heads * P));
-  const int nkt = (T + 63) / 64;
-  const size_t lds = (size_t)4 * 4096 * 2 + (size_t)nkt * (64 + 1) * 4;
-  a.nkt2 = (nkt + 1) & ~1;
-  a.bits = keep_bits;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const bool wide = ((uint64_t)P * heads * T * (uint64_t)((T + 3) & ~3)) / 4 + 64 >= (1ull << 32);
-  if (a.drop.thr && keep_bits)
-    hipLaunchKernelGGL((wide ? attn_fwd_bf16_kernel<2, true, true> : attn_fwd_bf16_kernel<2, false, true>),
-                       gq, dim3(256), lds, s, a);
-  else if (a.drop.thr)
-    hipLaunchKernelGGL((wide ? attn_fwd_bf16_kernel<1, true, true> : attn_fwd_bf16_kernel<1, false, true>),
-                       gq, dim3(256), lds, s, a);
-  else
-    hipLaunchKernelGGL((attn_fwd_bf16_kernel<0, false, true>), gq, dim3(256), lds, s, a);
+  launch_fwd(FWD16_Q8, attn_fwd_plan(P, T, T, heads, 1, a.drop.thr != 0, keep_bits != nullptr), a,
+             reinterpret_cast<hipStream_t>(stream));
   return mmseq_check_launch("attn_fwd_mxfp8");
 }
 

@@ -2,7 +2,8 @@
 // sum of squares (clip_grad_norm_), fused AdamW over the flat parameter buffer.
 #include <math.h>
 
-#include "common.h"
+#include "launch_plan.h"
+#include "reduce.h"
 
 namespace {
 
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(256) void transpose_batch_kernel(int n, const int64
   }
 }
 
-constexpr int CS_ROWS = 256;
+using mmseq_plan::CS_ROWS;
 // partial column sums over CS_ROWS rows: lane owns 8 columns (16-byte bf16 loads when VEC),
 // the 4 waves of the block stride over the rows and are combined through LDS.
 template <typename T, bool VEC>
@@ -249,13 +250,8 @@ extern "C" mmseq_status mmseq_transpose_cast_batch(int n, const int64_t* desc, i
   return mmseq_check_launch("transpose_cast_batch");
 }
 
-int64_t mmseq_reduce_extra(int nb, int W);
-mmseq_status mmseq_reduce_partials(int nb, int W, int split, const float* ws, float* ws2,
-                                   float* outA, float* outB, int accumulate, hipStream_t s);
-
 extern "C" int64_t mmseq_colsum_workspace(int rows, int cols) {
-  const int nb = (rows + CS_ROWS - 1) / CS_ROWS;
-  return (int64_t)nb * cols + mmseq_reduce_extra(nb, cols);
+  return mmseq_plan::colsum_plan(rows, cols).floats;
 }
 
 extern "C" mmseq_status mmseq_colsum(int rows, int cols, const void* x, int64_t ldx, float* out,
@@ -263,7 +259,8 @@ extern "C" mmseq_status mmseq_colsum(int rows, int cols, const void* x, int64_t 
                                      mmseq_stream stream) {
   MMSEQ_REQUIRE(rows >= 0 && cols > 0 && x && out && ws, "colsum: bad args");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int nb = (rows + CS_ROWS - 1) / CS_ROWS;
+  const mmseq_plan::ColsumPlan cp = mmseq_plan::colsum_plan(rows, cols);
+  const int nb = cp.nb;
   if (nb > 0) {
     dim3 grid((cols + 511) / 512, nb);
     const int esz = dt == MMSEQ_F32 ? 4 : 2;
@@ -286,8 +283,7 @@ extern "C" mmseq_status mmseq_colsum(int rows, int cols, const void* x, int64_t 
   }
   mmseq_status st = mmseq_check_launch("colsum");
   if (st) return st;
-  return mmseq_reduce_partials(nb, cols, cols, ws, ws + (int64_t)nb * cols, out, nullptr, accumulate,
-                               s);
+  return mmseq_reduce_partials(nb, cols, cols, ws, ws + cp.red_off, out, nullptr, accumulate, s);
 }
 
 extern "C" mmseq_status mmseq_act_fwd(int64_t n, int act, const void* x, void* y, mmseq_dtype dt,

@@ -3,18 +3,15 @@
 //   image: CLIP ViT patchify + class token + img_len=2 positional quirk + ln_pre
 //          (clip/model.py:262-278), with the per-pair image gather of
 //          process_images (process_inputs_for_berson.py:82-97) done on device.
-#include "common.h"
+#include "launch_plan.h"
+#include "reduce.h"
 #include <algorithm>
 #include <rocprim/device/device_radix_sort.hpp>
-
-mmseq_status ln_reduce_partials(int nb, int cols, const float* ws, float* dg, float* db,
-                                hipStream_t s);
-int64_t mmseq_reduce_extra(int nb, int W);
 
 namespace {
 
 constexpr int MAXV = 16;
-constexpr int RPB = 64;
+constexpr int RPB = mmseq_plan::EMBED_RPB;  // rows per workgroup of the backward kernels, by their name for it
 typedef unsigned short us;
 
 // ---------------------------------------------------------------------------------------------
@@ -699,10 +696,6 @@ __global__ __launch_bounds__(256) void vit_pos_fold_kernel(int W, int gg, const 
 
 }  // namespace
 
-extern "C" mmseq_status mmseq_colsum(int rows, int cols, const void* x, int64_t ldx, float* out,
-                                     int accumulate, float* ws, mmseq_dtype dt, mmseq_stream stream);
-extern "C" int64_t mmseq_colsum_workspace(int rows, int cols);
-
 extern "C" mmseq_status mmseq_embed_ln_fwd(int P, int Lt, int H, const int64_t* ids,
                                            const int64_t* tt, const float* word, const float* pos,
                                            const float* type, const float* gamma,
@@ -728,13 +721,7 @@ extern "C" mmseq_status mmseq_embed_ln_fwd(int P, int Lt, int H, const int64_t* 
 }
 
 extern "C" int64_t mmseq_embed_ln_bwd_workspace(int P, int Lt, int H) {
-  const int64_t rows = (int64_t)P * Lt;
-  const int nb = (int)((rows + RPB - 1) / RPB);
-  // de | LN partials + reduction scratch | the column-sum scratch of dpos | the table scatter's
-  // keys, sort scratch and pieces (floats, 16-byte aligned)
-  const int64_t cs = Lt > 1 ? mmseq_colsum_workspace(P, (Lt - 1) * H) : 0;
-  const int64_t head = (rows * H + (int64_t)nb * 2 * H + mmseq_reduce_extra(nb, 2 * H) + cs + 3) & ~3ll;
-  return head + (table_scatter_det_bytes(rows, H) + 3) / 4;
+  return mmseq_plan::embed_ln_bwd_layout(P, Lt, H, table_scatter_det_bytes((int64_t)P * Lt, H)).total;
 }
 
 extern "C" mmseq_status mmseq_embed_ln_bwd(int P, int Lt, int H, const int64_t* ids,
@@ -756,9 +743,11 @@ extern "C" mmseq_status mmseq_embed_ln_bwd(int P, int Lt, int H, const int64_t* 
   if (P == 0) return MMSEQ_OK;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int64_t rows = (int64_t)P * Lt;
-  const int nb = (int)((rows + RPB - 1) / RPB);
-  float* ws_de = workspace;
-  float* ws_ln = workspace + rows * H;
+  const mmseq_plan::EmbedLnBwdLayout wl =
+      mmseq_plan::embed_ln_bwd_layout(P, Lt, H, table_scatter_det_bytes(rows, H));
+  const int nb = wl.nb;
+  float* ws_de = workspace + wl.de;
+  float* ws_ln = workspace + wl.ln;
   if (dtype == MMSEQ_F32)
     hipLaunchKernelGGL(embed_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, P, Lt, H, ids, tt,
                        word, pos, type, gamma, mean, rstd, (const float*)djoint, ld_pair,
@@ -770,9 +759,7 @@ extern "C" mmseq_status mmseq_embed_ln_bwd(int P, int Lt, int H, const int64_t* 
   mmseq_status st = mmseq_check_launch("embed_ln_bwd");
   if (st) return st;
   {  // word / token-type tables: fixed-order sums per id (no float atomics)
-    const int64_t cs = Lt > 1 ? mmseq_colsum_workspace(P, (Lt - 1) * H) : 0;
-    const int64_t head = (rows * H + (int64_t)nb * 2 * H + mmseq_reduce_extra(nb, 2 * H) + cs + 3) & ~3ll;
-    void* tws = workspace + head;
+    void* tws = workspace + wl.scatter;
     st = table_scatter_det(rows, H, ids, ws_de, dword, tws, s);
     if (st) return st;
     if (tt && dtype_tab) {
@@ -783,8 +770,8 @@ extern "C" mmseq_status mmseq_embed_ln_bwd(int P, int Lt, int H, const int64_t* 
   // dpos[t] += sum_p de[p][t] for t >= 1 (row 0 = padding_idx): a deterministic column sum over the
   // P pairs of de viewed as [P][Lt * H] (a sequential loop over P per column was latency-bound)
   if (Lt > 1) {
-    float* cws = ws_ln + (int64_t)nb * 2 * H + mmseq_reduce_extra(nb, 2 * H);
-    st = mmseq_colsum(P, (Lt - 1) * H, ws_de + H, (int64_t)Lt * H, dpos + H, 1, cws, MMSEQ_F32, stream);
+    st = mmseq_colsum(P, (Lt - 1) * H, ws_de + H, (int64_t)Lt * H, dpos + H, 1, workspace + wl.cs,
+                      MMSEQ_F32, stream);
     if (st) return st;
   }
   return ln_reduce_partials(nb, H, ws_ln, dgamma, dbeta, s);
@@ -852,12 +839,7 @@ extern "C" mmseq_status mmseq_vit_embed_fwd(int P, int ntok, int W, int npatch_i
 }
 
 extern "C" int64_t mmseq_vit_embed_bwd_workspace(int P, int ntok, int W) {
-  const int64_t rows = (int64_t)P * ntok;
-  const int nb = (int)((rows + RPB - 1) / RPB);
-  // dx0 | LN partials + their reduction scratch | (bf16 path) sums over pairs of dpatch and dx0 +
-  // the column-sum scratch
-  const int64_t cs = std::max(mmseq_colsum_workspace(P, (ntok - 1) * W), mmseq_colsum_workspace(P, W));
-  return (int64_t)P * W + (int64_t)nb * 2 * W + mmseq_reduce_extra(nb, 2 * W) + (int64_t)ntok * W + cs;
+  return mmseq_plan::vit_embed_bwd_layout(P, ntok, W).total;
 }
 
 extern "C" mmseq_status mmseq_vit_embed_bwd(int P, int ntok, int W, int npatch_img,
@@ -870,10 +852,10 @@ extern "C" mmseq_status mmseq_vit_embed_bwd(int P, int ntok, int W, int npatch_i
   MMSEQ_REQUIRE(dy && x && dpatch_out && dcls && dpos && workspace, "vit_embed_bwd: null buffer");
   if (P == 0) return MMSEQ_OK;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int64_t rows = (int64_t)P * ntok;
-  const int nb = (int)((rows + RPB - 1) / RPB);
-  float* dx0 = workspace;
-  float* ws_ln = workspace + (int64_t)P * W;
+  const mmseq_plan::VitEmbedBwdLayout wl = mmseq_plan::vit_embed_bwd_layout(P, ntok, W);
+  const int nb = wl.nb;
+  float* dx0 = workspace + wl.dx0;
+  float* ws_ln = workspace + wl.ln;
   dim3 gpos((W + 255) / 256, npatch_img + 2);
   if (dtype == MMSEQ_F32) {
     hipLaunchKernelGGL(vit_embed_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, P, ntok, W,
@@ -890,9 +872,7 @@ extern "C" mmseq_status mmseq_vit_embed_bwd(int P, int ntok, int W, int npatch_i
 #undef VEB
     mmseq_status st = mmseq_check_launch("vit_embed_bwd");
     if (st) return st;
-    float* sp = ws_ln + (int64_t)nb * 2 * W + mmseq_reduce_extra(nb, 2 * W);  // [(ntok - 1)][W]
-    float* s0 = sp + (int64_t)(ntok - 1) * W;                                   // [W]
-    float* cws = s0 + W;
+    float *sp = workspace + wl.sp, *s0 = workspace + wl.s0, *cws = workspace + wl.cs;
     st = mmseq_colsum(P, (ntok - 1) * W, dpatch_out, (int64_t)(ntok - 1) * W, sp, 0, cws, MMSEQ_BF16,
                       stream);
     if (st) return st;

@@ -6,11 +6,14 @@
 // Lane l owns columns j*256 + 4l .. +3 (j < 4): 8-byte (bf16) / 16-byte (f32) accesses when the
 // row layout allows it (VEC), scalar otherwise; cols <= 256 * MJ (MJ = 4 up to 1024 columns, 8 up
 // to 2048: the 2H-wide MRM head LayerNorm of the pretraining path).
-#include "common.h"
+#include "launch_plan.h"
+#include "reduce.h"
 
 namespace {
 
-constexpr int RPB = 128;  // rows per workgroup in bwd (dgamma/dbeta partial granularity)
+using mmseq_plan::LnBwdPlan;
+// rows per workgroup of ln_bwd_kernel (dgamma/dbeta partial granularity), by the kernel's name for it
+constexpr int RPB = mmseq_plan::LN_RPB;
 
 // 32-bit division (rows < 2^31): a 64-bit divide is a ~100-instruction branchy subroutine
 __device__ __forceinline__ int64_t row_off(const mmseq_rows& l, int64_t r) {
@@ -369,7 +372,6 @@ __global__ __launch_bounds__(256) void ln_fwd16_q8_kernel(int rows, int cols,
 // dx = rstd * (g*dy - mean_c(g*dy) - xhat * mean_c(g*dy*xhat)) (+ dres); rpb rows per block,
 // each half wave walks rows hw, hw + 8, ... with the next row's loads issued before the current
 // row's math; per-block dgamma / dbeta partials -> ws[block][2][cols]
-constexpr int RPB16 = 64;
 // Q8 (config 5's fp8 dgrad): the gradient the next data-gradient GEMM reads (dxd when written, else
 // dx with the residual) also leaves in MX-fp8 (mmseq_quant_mxfp8 of the bf16 values: q [rows][ldq],
 // packed scales; the padding rows' scales are the caller's, zero-initialised)
@@ -551,13 +553,28 @@ bool rows_vec(const void* p, const mmseq_rows& l, int esz) {
   return ((uintptr_t)p % (4 * esz)) == 0 && l.ld % 4 == 0 && l.bstride % 4 == 0;
 }
 
+// The ln_bwd16_kernel of a plan: (DIN, DXD) freely, with or without Q8; CS only without input
+// dropout and Q8, and only up to NJ = 3 (at cols 1024 it would spill)
+typedef void (*LnBwd16)(int, int, int, const us*, mmseq_rows, const us*, mmseq_rows, const float*,
+                        const float*, const float*, us*, mmseq_rows, const us*, mmseq_rows, float*, Drop,
+                        us*, mmseq_rows, Drop, uint8_t*, int64_t, uint8_t*);
+
+template <int NJ, bool Q8>
+LnBwd16 ln_bwd16_of(bool din, bool dxd) {
+  return din ? (dxd ? ln_bwd16_kernel<NJ, true, true, Q8> : ln_bwd16_kernel<NJ, true, false, Q8>)
+             : (dxd ? ln_bwd16_kernel<NJ, false, true, Q8> : ln_bwd16_kernel<NJ, false, false, Q8>);
+}
+
+template <int NJ>
+LnBwd16 ln_bwd16_of(const LnBwdPlan& p) {
+  if constexpr (NJ <= 3)
+    if (p.cs)
+      return p.dxd ? ln_bwd16_kernel<NJ, false, true, false, true> : ln_bwd16_kernel<NJ, false, false, false, true>;
+  return p.q8 ? ln_bwd16_of<NJ, true>(p.din, p.dxd) : ln_bwd16_of<NJ, false>(p.din, p.dxd);
+}
+
 }  // namespace
 
-int64_t mmseq_reduce_extra(int nb, int W);
-mmseq_status mmseq_reduce_partials(int nb, int W, int split, const float* ws, float* ws2,
-                                   float* outA, float* outB, int accumulate, hipStream_t s);
-
-// ws must hold nb*2*cols partials followed by mmseq_reduce_extra(nb, 2*cols) scratch floats
 mmseq_status ln_reduce_partials(int nb, int cols, const float* ws, float* dg, float* db,
                                 hipStream_t s) {
   return mmseq_reduce_partials(nb, 2 * cols, cols, ws, const_cast<float*>(ws) + (int64_t)nb * 2 * cols,
@@ -607,20 +624,8 @@ extern "C" mmseq_status mmseq_layernorm_fwd(int rows, int cols, const void* x, m
   return mmseq_check_launch("layernorm_fwd");
 }
 
-extern "C" int64_t mmseq_colsum_workspace(int rows, int cols);
-mmseq_status mmseq_reduce_partials3(int nb, int W, int split, int split2, const float* ws, float* ws2,
-                                    float* outA, float* outB, float* outC, int accumulate,
-                                    hipStream_t s);
-extern "C" mmseq_status mmseq_colsum(int rows, int cols, const void* x, int64_t ldx, float* out,
-                                     int accumulate, float* ws, mmseq_dtype dt, mmseq_stream stream);
-
 extern "C" int64_t mmseq_layernorm_bwd_workspace(int rows, int cols) {
-  const int nb = (rows + RPB16 - 1) / RPB16;  // the bf16 fast path's block count (>= the generic)
-  // three partial rows per block (dgamma, dbeta, the written gradient's column sums) or, where the
-  // fast kernel does not take the column sums, the separate column-sum pass's workspace
-  const int64_t w = (int64_t)nb * 3 * cols + mmseq_reduce_extra(nb, 3 * cols);
-  const int64_t c = mmseq_colsum_workspace(rows, cols);
-  return w > c ? w : c;
+  return mmseq_plan::ln_bwd_workspace(rows, cols);
 }
 
 static mmseq_status layernorm_bwd_impl(int rows, int cols, const void* dy, mmseq_rows dyl,
@@ -641,92 +646,53 @@ static mmseq_status layernorm_bwd_impl(int rows, int cols, const void* dy, mmseq
                 "layernorm_bwd: dsum needs the summed gradient in dense rows");
   if (!dres) dresl = dxl;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int nb = (rows + RPB - 1) / RPB;
   const int esz = dtype == MMSEQ_BF16 ? 2 : 4;
   const bool vec = cols % 4 == 0 && rows_vec(dy, dyl, esz) && rows_vec(x, xl, esz) &&
                    rows_vec(dx, dxl, esz) && (!dres || rows_vec(dres, dresl, esz)) &&
                    (!dx_drop || rows_vec(dx_drop, dxdl, esz));
   const Drop din = make_drop(drop_dy), dout = make_drop(drop_dx);
-  if (dtype == MMSEQ_BF16 && cols % 256 == 0 && cols <= 1024 && rows_vec16(dy, dyl) && rows_vec16(x, xl) &&
-      rows_vec16(dx, dxl) && (!dres || rows_vec16(dres, dresl)) &&
-      (!dx_drop || rows_vec16(dx_drop, dxdl)) && ((uintptr_t)gamma % 16) == 0) {
-    // at most 512 blocks (two per CU at this kernel's ~190 VGPRs: one resident round), each over
-    // rpb rows: 2.5-10x fewer dgamma / dbeta partial rows to write and reduce than 64-row blocks
-    int rpb = RPB16, nb16 = (rows + RPB16 - 1) / RPB16;
-    if (nb16 > 512) {
-      rpb = ((rows + 511) / 512 + 7) / 8 * 8;
-      nb16 = (rows + rpb - 1) / rpb;
-    }
-    const bool di = din.thr != 0, dd = dx_drop != nullptr;
-    // the column sums ride in the kernel where it has the registers (no input dropout, bf16 out)
-    const bool cs = dsum && !q && !di && cols <= 768;  // at cols 1024 it would spill
-#define LNB16C(NJ, B) hipLaunchKernelGGL((ln_bwd16_kernel<NJ, false, B, false, true>), dim3(nb16), dim3(256), \
-                    0, s, rows, cols, rpb, (const us*)dy, dyl, (const us*)x, xl, mean, rstd, gamma, (us*)dx,  \
-                    dxl, (const us*)dres, dresl, workspace, din, (us*)dx_drop, dxdl, dout, nullptr, 0, nullptr)
-#define LNB16K(NJ, A, B) hipLaunchKernelGGL((ln_bwd16_kernel<NJ, A, B>), dim3(nb16), dim3(256), 0, s, rows, \
-                    cols, rpb, (const us*)dy, dyl, (const us*)x, xl, mean, rstd, gamma, (us*)dx, dxl,         \
-                    (const us*)dres, dresl, workspace, din, (us*)dx_drop, dxdl, dout, nullptr, 0, nullptr)
-#define LNB16Q(NJ, A, B) hipLaunchKernelGGL((ln_bwd16_kernel<NJ, A, B, true>), dim3(nb16), dim3(256), 0, s, \
-                    rows, cols, rpb, (const us*)dy, dyl, (const us*)x, xl, mean, rstd, gamma, (us*)dx, dxl,   \
-                    (const us*)dres, dresl, workspace, din, (us*)dx_drop, dxdl, dout, (uint8_t*)q, ldq, \
-                    (uint8_t*)q_scales)
-#define LNB16(NJ)                                           \
-  if (cs) {                                                 \
-    if (dd) LNB16C(NJ, true);                               \
-    else LNB16C(NJ, false);                                 \
-  } else LNB16N(NJ)
-#define LNB16N(NJ)                                          \
-  if (q) {                                                  \
-    if (di && dd) LNB16Q(NJ, true, true);                   \
-    else if (di) LNB16Q(NJ, true, false);                   \
-    else if (dd) LNB16Q(NJ, false, true);                   \
-    else LNB16Q(NJ, false, false);                          \
-  } else if (di && dd) LNB16K(NJ, true, true);              \
-  else if (di) LNB16K(NJ, true, false);                     \
-  else if (dd) LNB16K(NJ, false, true);                     \
-  else LNB16K(NJ, false, false);                            \
-  break
+  const bool fast16 = dtype == MMSEQ_BF16 && cols % 256 == 0 && cols <= 1024 && rows_vec16(dy, dyl) &&
+                      rows_vec16(x, xl) && rows_vec16(dx, dxl) && (!dres || rows_vec16(dres, dresl)) &&
+                      (!dx_drop || rows_vec16(dx_drop, dxdl)) && ((uintptr_t)gamma % 16) == 0;
+  if (q && !fast16)
+    return mmseq_set_error(MMSEQ_EUNSUPPORTED, "layernorm_bwd_mxfp8: bf16, cols 256..1024 (x256), 16-byte rows");
+  const LnBwdPlan lp = mmseq_plan::ln_bwd_plan(rows, cols, fast16, dsum, q, din.thr != 0, dx_drop);
+  if (lp.fast) {
+    LnBwd16 k = nullptr;
     switch (cols / 256) {
-      case 1: LNB16(1); case 2: LNB16(2); case 3: LNB16(3); case 4: LNB16N(4);
+      case 1: k = ln_bwd16_of<1>(lp); break;
+      case 2: k = ln_bwd16_of<2>(lp); break;
+      case 3: k = ln_bwd16_of<3>(lp); break;
+      case 4: k = ln_bwd16_of<4>(lp); break;
     }
-#undef LNB16
-#undef LNB16N
-#undef LNB16Q
-#undef LNB16K
-#undef LNB16C
-    mmseq_status st = mmseq_check_launch("layernorm_bwd");
-    if (st) return st;
-    if (cs)
-      return mmseq_reduce_partials3(nb16, 3 * cols, cols, 2 * cols, workspace,
-                                    workspace + (int64_t)nb16 * 3 * cols, dgamma, dbeta, dsum, 1, s);
-    if (dgamma || dbeta) {
-      st = ln_reduce_partials(nb16, cols, workspace, dgamma, dbeta, s);
-      if (st) return st;
-    }
-    // column sums as their own pass over the written gradient (the workspace is free again)
-    if (dsum) return mmseq_colsum(rows, cols, dx_drop ? dx_drop : dx, gl.ld, dsum, 1, workspace, dtype, stream);
-    return MMSEQ_OK;
-  }
-  if (q) return mmseq_set_error(MMSEQ_EUNSUPPORTED, "layernorm_bwd_mxfp8: bf16, cols 256..1024 (x256), 16-byte rows");
-#define LNBJ(T, V, J)                                                                             \
-  hipLaunchKernelGGL((ln_bwd_kernel<T, V, J>), dim3(nb), dim3(256), 0, s, rows, cols, (const T*)dy, \
-                     dyl, (const T*)x, xl, mean, rstd, gamma, (T*)dx, dxl, (const T*)dres, dresl,   \
+    hipLaunchKernelGGL(k, dim3(lp.nb), dim3(256), 0, s, rows, cols, lp.rpb, (const us*)dy, dyl, (const us*)x,
+                       xl, mean, rstd, gamma, (us*)dx, dxl, (const us*)dres, dresl, workspace, din,
+                       (us*)dx_drop, dxdl, dout, (uint8_t*)q, ldq, (uint8_t*)q_scales);
+  } else {
+#define LNBJ(T, V, J)                                                                                \
+  hipLaunchKernelGGL((ln_bwd_kernel<T, V, J>), dim3(lp.nb), dim3(256), 0, s, rows, cols, (const T*)dy, \
+                     dyl, (const T*)x, xl, mean, rstd, gamma, (T*)dx, dxl, (const T*)dres, dresl,      \
                      workspace, din, (T*)dx_drop, dxdl, dout)
 #define LNB(T, V) \
   if (cols <= 1024) { LNBJ(T, V, 4); } else { LNBJ(T, V, 8); }
-  if (dtype == MMSEQ_F32) {
-    if (vec) { LNB(float, true); } else { LNB(float, false); }
-  } else {
-    if (vec) { LNB(unsigned short, true); } else { LNB(unsigned short, false); }
-  }
+    if (dtype == MMSEQ_F32) {
+      if (vec) { LNB(float, true); } else { LNB(float, false); }
+    } else {
+      if (vec) { LNB(unsigned short, true); } else { LNB(unsigned short, false); }
+    }
 #undef LNBJ
 #undef LNB
+  }
   mmseq_status st = mmseq_check_launch("layernorm_bwd");
   if (st) return st;
+  if (lp.cs)
+    return mmseq_reduce_partials3(lp.nb, 3 * cols, cols, 2 * cols, workspace, workspace + lp.red_off,
+                                  dgamma, dbeta, dsum, 1, s);
   if (dgamma || dbeta) {
-    st = ln_reduce_partials(nb, cols, workspace, dgamma, dbeta, s);
+    st = ln_reduce_partials(lp.nb, cols, workspace, dgamma, dbeta, s);
     if (st) return st;
   }
+  // column sums as their own pass over the written gradient (the workspace is free again)
   if (dsum) return mmseq_colsum(rows, cols, dx_drop ? dx_drop : dx, gl.ld, dsum, 1, workspace, dtype, stream);
   return MMSEQ_OK;
 }

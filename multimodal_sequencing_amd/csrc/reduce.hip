@@ -1,11 +1,12 @@
 // Deterministic column reductions of per-workgroup partial rows (bias / LayerNorm-affine
 // gradients): out[w] (+)= sum_b ws[b][w] for w < W, in a fixed order. Two levels so that the
 // first level has ~(W/64) x (nb/64) workgroups in flight instead of W/64 serial loops.
-#include "common.h"
+#include "reduce.h"
+#include "launch_plan.h"
 
 namespace {
 
-constexpr int RCH = 64;  // partial rows per level-1 workgroup
+using mmseq_plan::RCH;  // partial rows per level-1 workgroup
 
 __global__ __launch_bounds__(256) void reduce_l1_kernel(int nb, int W, const float* __restrict__ ws,
                                                         float* __restrict__ ws2) {
@@ -40,27 +41,16 @@ __global__ __launch_bounds__(256) void reduce_l2_kernel(int nb2, int W, int spli
 
 }  // namespace
 
-int64_t mmseq_reduce_extra(int nb, int W) { return (int64_t)((nb + RCH - 1) / RCH) * W; }
-
-// ws: [nb][W] partials; ws2: scratch of mmseq_reduce_extra(nb, W) floats.
-// columns [0, split) go to outA, [split, W) to outB (either may be NULL).
 mmseq_status mmseq_reduce_partials(int nb, int W, int split, const float* ws, float* ws2,
                                    float* outA, float* outB, int accumulate, hipStream_t s) {
-  if (W <= 0) return MMSEQ_OK;
-  const int nb2 = (nb + RCH - 1) / RCH;
-  if (nb > 0)
-    hipLaunchKernelGGL(reduce_l1_kernel, dim3((W + 63) / 64, nb2), dim3(256), 0, s, nb, W, ws, ws2);
-  hipLaunchKernelGGL(reduce_l2_kernel, dim3((W + 255) / 256), dim3(256), 0, s, nb > 0 ? nb2 : 0, W,
-                     split, W, ws2, outA, outB, nullptr, accumulate);
-  return mmseq_check_launch("reduce_partials");
+  return mmseq_reduce_partials3(nb, W, split, W, ws, ws2, outA, outB, nullptr, accumulate, s);
 }
 
-// three outputs: columns [0, split) to outA, [split, split2) to outB, [split2, W) to outC
 mmseq_status mmseq_reduce_partials3(int nb, int W, int split, int split2, const float* ws, float* ws2,
                                     float* outA, float* outB, float* outC, int accumulate,
                                     hipStream_t s) {
   if (W <= 0) return MMSEQ_OK;
-  const int nb2 = (nb + RCH - 1) / RCH;
+  const int nb2 = mmseq_plan::reduce_rows(nb);
   if (nb > 0)
     hipLaunchKernelGGL(reduce_l1_kernel, dim3((W + 63) / 64, nb2), dim3(256), 0, s, nb, W, ws, ws2);
   hipLaunchKernelGGL(reduce_l2_kernel, dim3((W + 255) / 256), dim3(256), 0, s, nb > 0 ? nb2 : 0, W,
