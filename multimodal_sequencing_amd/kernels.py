@@ -16,7 +16,7 @@ import torch
 
 from . import _native as N
 
-GELU, QGELU, TANH, GELU_TANH = 1, 2, 3, 4
+GELU, QGELU, TANH, GELU_TANH = (N.ACT[a] for a in ("gelu", "quickgelu", "tanh", "gelu_tanh"))
 
 
 def _rows(ld):

@@ -6,15 +6,8 @@ from multimodal_sequencing_amd import _native as nat
 EINVAL = -1
 p = nat._p
 d = nat._d
-
-
-def status(name, *args):
-    """The raw mmseq_status of an entry point (the stream is appended)."""
-    return getattr(nat.lib(), name)(*args, nat._stream())
-
-
-def call(name, *args):
-    nat._check(status(name, *args), name)
+status = nat._raw  # the raw mmseq_status of an entry point (the stream is appended)
+call = nat._call  # ... checked: raises NativeError on any failure
 
 
 def attn_fwd(P, T, heads, qkv, ld_qkv, offs, bias, scale, out, ld_out, lse, dtype, variant,

@@ -54,6 +54,10 @@ def test_abi_exports_every_declared_symbol():
         n = 0 if args.strip() in ("void", "") else len(args.split(","))
         assert len(_native._SIGS[name][1]) == n, name
     assert lib.mmseq_version().startswith(b"mmseq")
+    # _SIGS is itself parsed from the header: hold it to the recorded table, type for type
+    import test_binding_trace
+    assert sorted(_native._SIGS) == sorted(name for name, _ in protos)
+    assert test_binding_trace.signatures() == test_binding_trace.golden()["signatures"]
 
 
 _DISASM = []
